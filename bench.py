@@ -9,6 +9,12 @@ every rank runs batch 4.  Prints ONE JSON line on rank 0.
   python bench.py                                   # 1 GPU, defaults
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the workload).  Everything
+else it can measure -- calibration probes and three timing windows, the roofline / per-kernel table, the batch-1 / sampler /
+attention / config4 legs, the one-rank RCCL leg, the CPU baseline -- runs only with --full (each still switchable off by its
+--no-* flag).  --dump-outputs DIR writes what the last timed step computed (dump_outputs) for output-by-output comparisons
+of two builds: with the same arguments the inputs and the random draws of the timed steps are the same from run to run.
 """
 import argparse
 import json
@@ -34,6 +40,33 @@ def build_model(dev):
     torch.manual_seed(0)
     model = adp.DiffusionModel(net_t=adp.UNetV0, in_channels=2, channels=CHANNELS, factors=FACTORS, items=ITEMS)
     return model.to(dev)
+
+
+PREWARM_STEPS = 80      # replays (~1 s) in front of the --warmup steps: clocks and power management settle under the step's load
+DUMP_GRAD_SAMPLE = 1 << 22  # gradient elements in grad_sample.npy (16 MB of float32)
+
+
+def dump_outputs(out_dir, loss, params):
+    """Writes what a caller of the timed step receives -- its loss and the gradients of every parameter -- as .npy files
+    (~17 MB in all; the full gradients are 700 MB):
+      loss.npy         the step's loss, float32 [1];
+      grad_norms.npy   the L2 norm of each parameter's gradient, float64, in model.parameters() order (zeros: no gradient);
+      grad_sample.npy  float32 values of the gradients at DUMP_GRAD_SAMPLE positions of their concatenation (same order), drawn
+                       once from a CPU generator seeded with 0 -- the same positions in every run of the same model."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+    norms, ofs = [], 0
+    for p in params:
+        norms.append(flat[ofs:ofs + p.numel()].double().norm())
+        ofs += p.numel()
+    idx = torch.randint(flat.numel(), (min(DUMP_GRAD_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "grad_norms.npy"), torch.stack(norms).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "grad_sample.npy"), flat.index_select(0, idx.to(flat.device)).float().cpu().numpy())
+    del flat
+    torch.cuda.empty_cache()
 
 
 def _cpu_worker(threads: int, batch: int, nsteps: int) -> None:
@@ -971,6 +1004,12 @@ def main():
                                                           "default: graph on 1 GPU, eager with RCCL")
     ap.add_argument("--dp-overlap", action="store_true",
                     help="N > 1: also report dp_overlap = {step, step without all-reduce, all-reduce alone, hidden_frac}")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: calibration probes + three timing windows, roofline / "
+                         "per-kernel table, batch-1 / sampler / attention / config4 legs, one-rank RCCL leg, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and gradients as DIR/<name>.npy (dump_outputs)")
+    # (--no-cpu-baseline / --no-roofline / --no-extras / --no-calibration / --no-dp1 switch off one measurement of --full)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the batch-1 / sampler / attention legs")
@@ -1013,10 +1052,13 @@ def main():
         for p in model.parameters():
             p.grad = None
 
+    last = {}  # the loss tensor the timed step writes (the graph's static output when replayed)
+
     def eager_step():
         zero()
         loss = model(x)
         loss.backward()
+        last["loss"] = loss.detach()
         return loss
 
     graph = None
@@ -1041,6 +1083,7 @@ def main():
             #  capture stream -- alive, and every later eager backward in this process would run its 600 gradient accumulations
             #  on that stream behind an event pair each)
             static_loss = static_loss.detach()
+            last["loss"] = static_loss
         except Exception as e:  # capture is a launch-overhead optimisation only; the kernels are identical
             if rank == 0:
                 print(f"[bench] hipGraph capture unavailable ({type(e).__name__}: {e}); timing eager launches",
@@ -1075,15 +1118,18 @@ def main():
 
     calib = None
     if world == 1 and not args.no_calibration:
-        # >= 1 s of the step itself before anything is timed (clocks and power management settle under THIS load); the
-        # calibration probes run first, and the clocks are read while the pre-warm replays are queued
+        # >= 1 s of the step itself before anything is timed (clocks and power management settle under THIS load); with --full
+        # the calibration probes run first, and the clocks are read while the pre-warm replays are queued
         def busy():
-            for _ in range(80):
+            for _ in range(PREWARM_STEPS):
                 step()
-        try:
-            calib = calibration(dev, busy)
-        except Exception as e:
-            calib = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            try:
+                calib = calibration(dev, busy)
+            except Exception as e:
+                calib = {"error": f"{type(e).__name__}: {e}"}
+        else:
+            busy()
         torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
@@ -1101,9 +1147,11 @@ def main():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:  # (before anything else runs the step again)
+        dump_outputs(args.dump_outputs, last["loss"], list(model.parameters()))
 
     windows = [dt / args.steps * 1e3]
-    if world == 1 and not args.no_calibration:  # two more windows of the same K steps: is the first one representative?
+    if world == 1 and args.full and not args.no_calibration:  # two more windows of the same K steps: is the first one representative?
         for _ in range(2):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -1151,7 +1199,7 @@ def main():
     # wait in the closing barrier.  The instrumented steps run on the unwrapped module with the data-parallel hook detached
     # (one rank issuing collectives alone would hang the job).
     inner = model.module if world > 1 else model
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         hook_owner = model.unet if world > 1 else None
         hook = getattr(hook_owner, "_grad_ready_hook", None)
         try:
@@ -1174,13 +1222,13 @@ def main():
         finally:
             if hook_owner is not None:
                 hook_owner._grad_ready_hook = hook
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         legs = extra_legs(model, x, dev)
         line.update(legs)
         line["eager_api"] = eager_api_leg(model, x, min(windows), legs.get("batch1", {}).get("ms_per_step"))
-    if rank == 0 and world == 1 and not args.no_dp1:
+    if rank == 0 and world == 1 and args.full and not args.no_dp1:
         line["dp1"] = dp1_leg()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (N > 1: one thread setting, three steps -- the other ranks are waiting)
         line["cpu_baseline"] = cpu_baseline(args.batch) if world == 1 else cpu_baseline(args.batch, sweep=(16,), final_steps=3)
     if rank == 0:

@@ -1,4 +1,4 @@
-"""Generates tests/golden/vdiffusion_golden.pt from the LIVE reference modules
+"""Generates tests/golden/vdiffusion_golden.pt and live_reference_golden.pt from the LIVE reference modules
 (/root/reference/audio_diffusion_pytorch/diffusion.py and utils.py, loaded by oracle/reference_loader.py).
 Run in the build container only (the GPU box has no /root/reference):  python tests/golden/make_golden.py
 
@@ -78,5 +78,33 @@ def main():
     print("wrote", len(out), "entries; alpha0 =", float(a[0]), "sigma[1] =", float(out["linspace_51"][1]))
 
 
+def live_check():
+    """tests/golden/live_reference_golden.pt: the live reference's outputs on the inputs of
+    tests/test_oracle.py::test_oracle_matches_live_reference, so that the test runs where the reference is absent."""
+    D, U = load_reference()
+    net = StubNet()
+    g = torch.Generator().manual_seed(5)
+    out = {"x": torch.randn(2, 2, 96, generator=g)}
+    out["vs_out_7"] = D.VSampler(net)(out["x"], num_steps=7)
+    out["sigmas"] = sig = torch.tensor([0.21, 0.83])
+
+    class Fixed(D.Distribution):
+        def __call__(self, num_samples, device=torch.device("cpu")):
+            return sig
+
+    torch.manual_seed(3)
+    out["noise"] = torch.randn_like(out["x"])
+    torch.manual_seed(3)
+    out["vd_loss"] = D.VDiffusion(net, sigma_distribution=Fixed())(out["x"]).detach()
+    out["w"] = torch.randn(1, 2, 300, generator=g)
+    out["down_3"], out["up_3"] = U.downsample(out["w"], 3), U.upsample(out["w"], 3)
+    out["mask"] = torch.rand(2, 2, 96, generator=g) > 0.5
+    torch.manual_seed(11)
+    out["vi_out_5_2"] = D.VInpainter(net)(out["x"], out["mask"], num_steps=5, num_resamples=2)
+    torch.save(out, os.path.join(os.path.dirname(os.path.abspath(__file__)), "live_reference_golden.pt"))
+    print("wrote", len(out), "entries")
+
+
 if __name__ == "__main__":
     main()
+    live_check()

@@ -94,3 +94,38 @@ def test_bench_launches_its_own_ranks_when_no_launcher_did():
     assert "--nproc-per-node=4" in seen["cmd"] and seen["cmd"][-4:] == ["--gpus", "4", "--steps", "3"]
     assert seen["cmd"][seen["cmd"].index("--master-addr") + 1] == "127.0.0.1"
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_dump_outputs_writes_loss_and_gradient_sample(tmp_path):
+    """--dump-outputs: the loss, every parameter's gradient norm and a fixed sample of the gradients, float32 / float64 .npy;
+    the sampled positions do not depend on the run."""
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3, bias=False), torch.nn.Linear(3, 2))
+    loss = net[1](net[0](torch.randn(4, 7))).square().mean()  # (the last layer gets no gradient)
+    loss.backward()
+    params = list(net.parameters())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, params)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "grad_norms", "grad_sample")}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == (1,) and got["loss"][0] == np.float32(loss.item())
+    want = [p.grad.double().norm().item() if p.grad is not None else 0.0 for p in params]
+    assert got["grad_norms"].dtype == np.float64 and np.allclose(got["grad_norms"], want)
+    flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+    n = flat.numel()
+    assert got["grad_sample"].dtype == np.float32 and got["grad_sample"].shape == (min(n, bench.DUMP_GRAD_SAMPLE),)
+    assert set(got["grad_sample"].tolist()) <= set(flat.tolist())
+    for name, arr in got.items():
+        assert np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy")), name
+    # the whole dump of the benchmarked model stays far below 64 MB
+    assert 4 * bench.DUMP_GRAD_SAMPLE + 8 * 2000 + 4 < 64 << 20
+
+
+def test_plain_run_flags():
+    """`--full` (the measurements beyond the headline) and `--dump-outputs DIR` are part of bench.py's command line."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, bench.__file__, "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout

@@ -13,7 +13,7 @@ QUIET="--no-cpu-baseline --no-roofline --no-extras --no-calibration --no-dp1"
 bash tools/pmc.sh "$TAG" --no-calibration --no-dp1 > "$O/${TAG}_pmc.log" 2>&1
 [ -f "$O/pmc_$TAG/pmc_traffic.json" ] && cp "$O/pmc_$TAG/pmc_traffic.json" "$ROOT/profiles/pmc_traffic.json"
 python -m pytest tests -m gpu -x -q > "$O/${TAG}_gputests.txt" 2>&1; tail -3 "$O/${TAG}_gputests.txt"
-ADP_BENCH_DETAIL=$O/${TAG}_bench_b4_per_shape.txt python bench.py > "$O/${TAG}_bench_n1.json" 2> "$O/${TAG}_bench.err"
+ADP_BENCH_DETAIL=$O/${TAG}_bench_b4_per_shape.txt python bench.py --full > "$O/${TAG}_bench_n1.json" 2> "$O/${TAG}_bench.err"
 python tools/detail.py "$O/${TAG}_per_shape_b1_fwd.txt" --batch 1 --fwd > /dev/null 2>&1
 python tools/detail.py "$O/${TAG}_per_shape_b1.txt" --batch 1 > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp

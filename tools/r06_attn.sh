@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 python -m pytest tests/test_kernels.py -q -m gpu -k "attention" 2>&1 | tail -2 > gpurun_out/attn_tests.txt
 for fk in 0 1 0 1; do
-  ADP_ATTN_FEWKEYS=$fk python bench.py --no-cpu-baseline --no-dp1 --no-roofline --no-calibration 2>/dev/null | python -c "
+  ADP_ATTN_FEWKEYS=$fk python bench.py --full --no-cpu-baseline --no-dp1 --no-roofline --no-calibration 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 def find(o):

@@ -9,7 +9,7 @@ cd "$ROOT"
 python -m pytest tests/test_train_graph.py -m gpu -x -q > "$O/r06a_train_graph_tests.txt" 2>&1; tail -15 "$O/r06a_train_graph_tests.txt"
 python -m pytest tests -m gpu -x -q > "$O/r06a_gputests.txt" 2>&1; tail -3 "$O/r06a_gputests.txt"
 (timeout 120 python tools/graph_branch_probe.py) 2>&1 | grep "^\[" > "$O/r06a_graph_branch_probe.txt"; cat "$O/r06a_graph_branch_probe.txt"
-python bench.py > "$O/r06a_bench_n1.json" 2> "$O/r06a_bench.err"; tail -3 "$O/r06a_bench.err"
+python bench.py --full > "$O/r06a_bench_n1.json" 2> "$O/r06a_bench.err"; tail -3 "$O/r06a_bench.err"
 python - <<'PY'
 import json,os
 p=os.path.join(os.environ.get("GRAFT_REPO_ROOT","."),"gpurun_out","r06a_bench_n1.json")

@@ -7,7 +7,7 @@ cd "$ROOT"
 (timeout 300 python tools/ktrace.py run 1024 256 4) > "$O/r06b_ktrace_d7.txt" 2>&1; grep -v "Warn\|amdgpu.ids" "$O/r06b_ktrace_d7.txt"
 (timeout 300 python tools/ktrace.py run 512 1024 4) > "$O/r06b_ktrace_d5.txt" 2>&1; grep -v "Warn\|amdgpu.ids" "$O/r06b_ktrace_d5.txt" | head -70
 python -m pytest tests/test_train_graph.py -m gpu -x -q > "$O/r06b_train_graph_tests.txt" 2>&1; grep -v "Warn\|amdgpu.ids" "$O/r06b_train_graph_tests.txt" | head -60
-python bench.py --no-cpu-baseline --no-dp1 > "$O/r06b_bench_n1.json" 2> "$O/r06b_bench.err"; tail -3 "$O/r06b_bench.err"
+python bench.py --full --no-cpu-baseline --no-dp1 > "$O/r06b_bench_n1.json" 2> "$O/r06b_bench.err"; tail -3 "$O/r06b_bench.err"
 python - <<'PY'
 import json,os
 p=os.path.join(os.environ.get("GRAFT_REPO_ROOT","."),"gpurun_out","r06b_bench_n1.json")

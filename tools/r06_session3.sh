@@ -10,7 +10,7 @@ for tag in ""; do
 done
 python -m pytest tests/test_train_graph.py -m gpu -x -q > "$O/r06c_train_graph_tests.txt" 2>&1; tail -3 "$O/r06c_train_graph_tests.txt"
 python -m pytest tests/test_kernels.py -m gpu -x -q -k "mm4 or wgrad or dynamic_range" > "$O/r06c_kernel_tests.txt" 2>&1; tail -3 "$O/r06c_kernel_tests.txt"
-python bench.py --no-cpu-baseline --no-dp1 --no-extras > "$O/r06c_bench_n1.json" 2> "$O/r06c_bench.err"; tail -2 "$O/r06c_bench.err"
+python bench.py --full --no-cpu-baseline --no-dp1 --no-extras > "$O/r06c_bench_n1.json" 2> "$O/r06c_bench.err"; tail -2 "$O/r06c_bench.err"
 python - <<'PY'
 import json,os
 p=os.path.join(os.environ.get("GRAFT_REPO_ROOT","."),"gpurun_out","r06c_bench_n1.json")

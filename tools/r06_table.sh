@@ -2,7 +2,7 @@
 # kernel table of the headline step under an environment: tools/r06_table.sh "<ENV=.. ...>"
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$ROOT/gpurun_out; mkdir -p "$O"; cd "$ROOT"
-env $1 ADP_BENCH_DETAIL=$O/r06_detail.txt python bench.py --no-cpu-baseline --no-dp1 --no-extras --no-calibration 2>/dev/null | python -c "
+env $1 ADP_BENCH_DETAIL=$O/r06_detail.txt python bench.py --full --no-cpu-baseline --no-dp1 --no-extras --no-calibration 2>/dev/null | python -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value',l['value'],'ms',l['ms_per_step'],'instrumented',l.get('instrumented_kernel_ms_per_step'))
