@@ -100,6 +100,9 @@ SIGNATURES = {
     "adp_cfg_mix": (c_int, [P, I, F, P, P]),
     "adp_select_rows": (c_int, [P, P, P, I, I, P, P]),
     "adp_resample": (c_int, [P, P, I, I, I, I, I, I, I, P, P]),
+    "adp_stft_loss_ws_bytes": (I, [I, I, I, P, I]),
+    "adp_stft_loss_fwd": (c_int, [P, P, I, I, I, P, F, F, F, F, P, P, P]),
+    "adp_stft_loss_bwd": (c_int, [P, P, P, P, I, I, I, P, F, F, F, F, P, P, P]),
     "adp_ctx_fold_fwd": (c_int, [P, P, P, I, I, I, P, P, P]),
     "adp_ctx_fold_bwd": (c_int, [P, P, P, P, P, I, I, I, P, P, P, P]),
     "adp_attn_fwd": (c_int, [P, P, P, I, I, I, I, I, I, I, P, P, P, P]),

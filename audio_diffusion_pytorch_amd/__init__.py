@@ -12,6 +12,7 @@ from .diffusion import (
     VInpainter,
     VSampler,
 )
+from .losses import MultiResolutionSTFTLoss, STFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
 from .unet import UNetV0Net
 
@@ -42,5 +43,5 @@ __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
     "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "DiffusionModel", "DiffusionUpsampler",
     "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
-    "DiffusionAR", "LTPlugin",
+    "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss",
 ]

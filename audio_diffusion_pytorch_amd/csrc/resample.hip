@@ -61,3 +61,494 @@ extern "C" int adp_resample(const float* x, const float* kern, int64_t rows, int
   ADP_LAUNCH(resample_kernel, grid, dim3(256), stream, x, kern, length, (int)fi, (int)fo, (int)J, (int)width, out_len, out);
   return ADP_LAUNCH_OK();
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Multi-resolution STFT loss (losses.py; auraloss's MultiResolutionSTFTLoss with its defaults).  Per resolution
+// (N = fft size, h = hop, W = window length) and signal row:
+//
+//   X[t, k] = sum_n wt[n] * xpad[t*h + n] * e^{-2 pi i k n / N},   k <= N/2,  t < 1 + L/h
+//   wt      = periodic Hann of length W, zero-padded and centred in N;  xpad = x reflect-padded by N/2 on each side
+//   m       = sqrt(max(|X|^2, eps));   SC = ||m_y - m_x||_F / ||m_y||_F;   LM = mean|log m_x - log m_y|;
+//   LIN     = mean|m_x - m_y|;         loss = mean over resolutions of (w_sc SC + w_log LM + w_lin LIN)
+//
+// Transform: two consecutive real frames a, b of ONE signal are packed as z = a + i b into one N-point complex FFT and
+// separated afterwards (A[k] = (Z[k] + conj Z[N-k]) / 2, B[k] = -i (Z[k] - conj Z[N-k]) / 2): the same work as two
+// N/2-point complex FFTs plus their split steps.  x and y go through identical arithmetic, so x == y gives m_x == m_y
+// bit for bit (a zero loss and a zero gradient).  The FFT is a Stockham radix-4 (one radix-2 pass first when log2 N
+// is odd) over LDS: every thread takes its butterflies' operands into registers, barrier, writes them back, barrier.
+// Twiddles (N/4 entries, W^2 and W^3 by complex products) and the window are computed into LDS by each workgroup: no
+// host->device copy, so the first call may sit inside a stream capture.
+//
+// Forward: one launch per resolution.  A workgroup owns up to `fpb` consecutive frames of one row, stages their input
+// span of both signals in LDS (reflect padding = index arithmetic), runs 2 PAIRS frames per FFT pass and leaves four partial
+// sums (sum (m_y - m_x)^2, sum m_y^2, sum |log m_x - log m_y|, sum |m_x - m_y|) in the workspace; magnitudes never leave
+// the chip.  One single-wave launch reduces every resolution's partials in double in a fixed order, writes the loss and
+// keeps ||m_y - m_x|| and ||m_y|| per resolution for the backward pass.
+//
+// Backward (exact adjoint, input gradient only): one launch per resolution.  A workgroup owns PB consecutive samples of
+// the PADDED row and computes every frame that touches them: FFTs of the packed frame pairs of x and y, G = dL/dm * X / m
+// from the saved norms, the onesided inverse of a frame pair as one complex FFT of the conjugated S_a + i S_b (S: the
+// Hermitian extension of G, S[0] = Re G[0], S[N/2] = Re G[N/2], S[k] = G[k]/2, S[N-k] = conj G[k]/2; 1.5 transforms per
+// frame in all), window, and an overlap-add by gather into registers (frames in
+// increasing order; boundary frames are recomputed by both neighbours, no atomics).  A last launch folds the reflect-pad
+// edges back onto the mirrored samples and sums the resolutions, in a fixed order.  Everything is deterministic.
+namespace {
+
+constexpr int ST_MAXR = 4;          // resolutions per call
+constexpr int ST_SPAN_EXTRA = 2048; // staged input floats per signal beyond one frame (forward)
+
+struct StftPlan {
+  int nres;
+  int n[ST_MAXR], logn[ST_MAXR], hop[ST_MAXR], win[ST_MAXR];
+  int frames[ST_MAXR];       // 1 + L / h
+  int fpb[ST_MAXR];          // frames per forward workgroup
+  int chunks[ST_MAXR];       // forward workgroups per row
+  int64_t part_off[ST_MAXR]; // float offset of the resolution's forward partials in the forward workspace
+  int64_t gp_off[ST_MAXR];   // float offset of the resolution's padded-row gradient in the backward workspace
+  int64_t rows, length;
+  float w_sc, w_log, w_lin, eps;
+};
+
+constexpr int ST_NORMS = 2 * ST_MAXR;  // forward workspace head: ||m_y - m_x||, ||m_y|| per resolution
+
+template <int LOGN>
+struct StftCfg {
+  static constexpr int N = 1 << LOGN;
+  static constexpr int PAIRS = N >= 512 ? 1 : 512 / N;  // frame pairs per FFT pass (2 PAIRS transforms: >= 256 butterflies)
+  static constexpr int XCAP = N + ST_SPAN_EXTRA;        // staged floats per signal (forward)
+  static constexpr int PB = N >= 1024 ? 2 * N : 2048;   // padded samples per backward workgroup
+};
+
+__device__ __forceinline__ int64_t st_reflect(int64_t i, int64_t L) {
+  if (i < 0) i = -i;
+  if (i >= L) i = 2 * (L - 1) - i;
+  return i;
+}
+
+// twr/twi[m] = e^{-2 pi i m / N}, m < N/4; win = periodic Hann of length W centred in N (torch.stft's zero padding)
+template <int LOGN>
+__device__ void st_tables(float* twr, float* twi, float* win, int W) {
+  constexpr int N = 1 << LOGN;
+  const int off = (N - W) / 2;
+  for (int m = threadIdx.x; m < N / 4; m += 256) {
+    const float a = (float)m * (6.28318530717958647692f / (float)N);
+    twr[m] = cosf(a);
+    twi[m] = -sinf(a);
+  }
+  for (int n = threadIdx.x; n < N; n += 256) {
+    const int m = n - off;
+    win[n] = (m >= 0 && m < W) ? 0.5f - 0.5f * cosf((float)m * (6.28318530717958647692f / (float)W)) : 0.0f;
+  }
+}
+
+// in-place forward FFT of NB consecutive N-point complex sequences (re/im) by the whole workgroup; starts after a barrier
+// that published the input, ends with a barrier
+template <int LOGN, int NB>
+__device__ void st_fft(float* re, float* im, const float* twr, const float* twi) {
+  constexpr int N = 1 << LOGN;
+  const int tid = threadIdx.x;
+  int Ns = 1;
+  if (LOGN & 1) {  // radix-2 pass with unit twiddles
+    constexpr int NBF = NB * N / 2;
+    constexpr int PER = (NBF + 255) / 256;
+    float ar[PER][2], ai[PER][2];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int g = tid + q * 256;
+      if (g < NBF) {
+        const int base = (g >> (LOGN - 1)) << LOGN, j = g & (N / 2 - 1);
+        const float r0 = re[base + j], i0 = im[base + j], r1 = re[base + j + N / 2], i1 = im[base + j + N / 2];
+        ar[q][0] = r0 + r1; ai[q][0] = i0 + i1;
+        ar[q][1] = r0 - r1; ai[q][1] = i0 - i1;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int g = tid + q * 256;
+      if (g < NBF) {
+        const int base = (g >> (LOGN - 1)) << LOGN, j = g & (N / 2 - 1);
+        re[base + 2 * j] = ar[q][0]; im[base + 2 * j] = ai[q][0];
+        re[base + 2 * j + 1] = ar[q][1]; im[base + 2 * j + 1] = ai[q][1];
+      }
+    }
+    __syncthreads();
+    Ns = 2;
+  }
+  constexpr int NBF = NB * N / 4;
+  constexpr int PER = (NBF + 255) / 256;
+  for (; Ns < N; Ns *= 4) {
+    float vr[PER][4], vi[PER][4];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int g = tid + q * 256;
+      if (g < NBF) {
+        const int base = (g >> (LOGN - 2)) << LOGN, j = g & (N / 4 - 1), k = j & (Ns - 1);
+        const int t = k * (N / (4 * Ns));
+        const float w1r = twr[t], w1i = twi[t];
+        const float w2r = w1r * w1r - w1i * w1i, w2i = 2.0f * w1r * w1i;
+        const float w3r = w1r * w2r - w1i * w2i, w3i = w1r * w2i + w1i * w2r;
+        const float x0r = re[base + j], x0i = im[base + j];
+        const float u1r = re[base + j + N / 4], u1i = im[base + j + N / 4];
+        const float u2r = re[base + j + N / 2], u2i = im[base + j + N / 2];
+        const float u3r = re[base + j + 3 * N / 4], u3i = im[base + j + 3 * N / 4];
+        const float x1r = u1r * w1r - u1i * w1i, x1i = u1r * w1i + u1i * w1r;
+        const float x2r = u2r * w2r - u2i * w2i, x2i = u2r * w2i + u2i * w2r;
+        const float x3r = u3r * w3r - u3i * w3i, x3i = u3r * w3i + u3i * w3r;
+        const float a0r = x0r + x2r, a0i = x0i + x2i, a1r = x0r - x2r, a1i = x0i - x2i;
+        const float a2r = x1r + x3r, a2i = x1i + x3i;
+        const float a3r = x1i - x3i, a3i = x3r - x1r;  // (x1 - x3) * (-i)
+        vr[q][0] = a0r + a2r; vi[q][0] = a0i + a2i;
+        vr[q][1] = a1r + a3r; vi[q][1] = a1i + a3i;
+        vr[q][2] = a0r - a2r; vi[q][2] = a0i - a2i;
+        vr[q][3] = a1r - a3r; vi[q][3] = a1i - a3i;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int g = tid + q * 256;
+      if (g < NBF) {
+        const int base = (g >> (LOGN - 2)) << LOGN, j = g & (N / 4 - 1), k = j & (Ns - 1);
+        const int d = base + (j - k) * 4 + k;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          re[d + r * Ns] = vr[q][r];
+          im[d + r * Ns] = vi[q][r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// bin k (<= N/2) of the two real frames packed in one transform Z
+template <int LOGN>
+__device__ __forceinline__ void st_split(const float* re, const float* im, int k, float& xr, float& xi, float& yr,
+                                         float& yi) {
+  constexpr int N = 1 << LOGN;
+  const int kc = (N - k) & (N - 1);
+  const float zr = re[k], zi = im[k], cr = re[kc], ci = -im[kc];
+  xr = 0.5f * (zr + cr);
+  xi = 0.5f * (zi + ci);
+  yr = 0.5f * (zi - ci);
+  yi = -0.5f * (zr - cr);
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(256) void stft_fwd_kernel(const float* x, const float* y, StftPlan p, int r, float* ws) {
+  using C = StftCfg<LOGN>;
+  constexpr int N = C::N, NP = C::PAIRS, NK = N / 2 + 1;
+  __shared__ float xs[C::XCAP];
+  __shared__ float ys[C::XCAP];
+  __shared__ float bre[2 * NP * N];  // transforms [0, NP): pairs of x frames; [NP, 2 NP): the same pairs of y frames
+  __shared__ float bim[2 * NP * N];
+  __shared__ float twr[N / 4];
+  __shared__ float twi[N / 4];
+  __shared__ float win[N];
+  __shared__ float red[4][4];
+  const int tid = threadIdx.x;
+  const int hop = p.hop[r], fpb = p.fpb[r];
+  const int64_t row = blockIdx.y, L = p.length;
+  const int f0 = blockIdx.x * fpb;
+  const int nf = (p.frames[r] - f0 < fpb) ? p.frames[r] - f0 : fpb;
+  const float eps = p.eps;
+  st_tables<LOGN>(twr, twi, win, p.win[r]);
+  const int64_t s0 = (int64_t)f0 * hop - N / 2;  // original-signal index of the span's first (padded) sample
+  const int span = (nf - 1) * hop + N;
+  const float* xr = x + row * L;
+  const float* yr = y + row * L;
+  for (int i = tid; i < span; i += 256) {
+    const int64_t src = st_reflect(s0 + i, L);
+    xs[i] = xr[src];
+    ys[i] = yr[src];
+  }
+  __syncthreads();
+  float s_d = 0.0f, s_y = 0.0f, s_log = 0.0f, s_lin = 0.0f;
+  for (int fb = 0; fb < nf; fb += 2 * NP) {
+    for (int i = tid; i < 2 * NP * N; i += 256) {
+      const int s = i >> LOGN, n = i & (N - 1);
+      const int ta = fb + 2 * (s % NP);  // frames ta, ta + 1 of x (s < NP) or of y
+      const float* src = s < NP ? xs : ys;
+      bre[i] = ta < nf ? win[n] * src[ta * hop + n] : 0.0f;
+      bim[i] = ta + 1 < nf ? win[n] * src[(ta + 1) * hop + n] : 0.0f;
+    }
+    __syncthreads();
+    st_fft<LOGN, 2 * NP>(bre, bim, twr, twi);
+    for (int i = tid; i < NP * NK; i += 256) {
+      const int s = i / NK, k = i - s * NK;
+      const int ta = fb + 2 * s;
+      if (ta >= nf) continue;
+      float X[2][2], Y[2][2];  // [frame ta / ta + 1][re, im]
+      st_split<LOGN>(bre + s * N, bim + s * N, k, X[0][0], X[0][1], X[1][0], X[1][1]);
+      st_split<LOGN>(bre + (NP + s) * N, bim + (NP + s) * N, k, Y[0][0], Y[0][1], Y[1][0], Y[1][1]);
+      for (int e = 0; e < 2 && ta + e < nf; ++e) {
+        const float mx = sqrtf(fmaxf(X[e][0] * X[e][0] + X[e][1] * X[e][1], eps));
+        const float my = sqrtf(fmaxf(Y[e][0] * Y[e][0] + Y[e][1] * Y[e][1], eps));
+        const float d = my - mx;
+        s_d = fmaf(d, d, s_d);
+        s_y = fmaf(my, my, s_y);
+        s_log += fabsf(logf(mx) - logf(my));
+        s_lin += fabsf(mx - my);
+      }
+    }
+    __syncthreads();
+  }
+  s_d = adp_wave_sum(s_d);
+  s_y = adp_wave_sum(s_y);
+  s_log = adp_wave_sum(s_log);
+  s_lin = adp_wave_sum(s_lin);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = s_d;
+    red[tid >> 6][1] = s_y;
+    red[tid >> 6][2] = s_log;
+    red[tid >> 6][3] = s_lin;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    float* out = ws + p.part_off[r] + (row * p.chunks[r] + blockIdx.x) * 4;
+    out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  }
+}
+
+// one wave: every resolution's partials in double, lane-strided then in lane order (fixed order), -> loss and norms
+__global__ __launch_bounds__(64) void stft_final_kernel(float* ws, StftPlan p, float* loss) {
+  __shared__ double part[64];
+  const int tid = threadIdx.x;
+  double total = 0.0;
+  for (int r = 0; r < p.nres; ++r) {
+    const int64_t nb = p.rows * p.chunks[r];
+    const float* src = ws + p.part_off[r];
+    double q[4];
+    for (int c = 0; c < 4; ++c) {
+      double s = 0.0;
+      for (int64_t i = tid; i < nb; i += 64) s += (double)src[i * 4 + c];
+      part[tid] = s;
+      __syncthreads();
+      double t = 0.0;
+      for (int i = 0; i < 64; ++i) t += part[i];
+      q[c] = t;
+      __syncthreads();
+    }
+    const double count = (double)p.rows * (double)p.frames[r] * (double)(p.n[r] / 2 + 1);
+    const double nd = sqrt(q[0]), ny = sqrt(q[1]);
+    total += (double)p.w_sc * (nd / ny) + (double)p.w_log * (q[2] / count) + (double)p.w_lin * (q[3] / count);
+    if (tid == 0) {
+      ws[2 * r] = (float)nd;
+      ws[2 * r + 1] = (float)ny;
+    }
+  }
+  if (tid == 0) loss[0] = (float)(total / (double)p.nres);
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(256) void stft_bwd_kernel(const float* x, const float* y, const float* gloss,
+                                                       const float* norms, StftPlan p, int r, float* ws) {
+  using C = StftCfg<LOGN>;
+  constexpr int N = C::N, NP = C::PAIRS, NK = N / 2 + 1, PB = C::PB, NACC = PB / 256;
+  __shared__ float bre[2 * NP * N];  // as in the forward: x pairs, then the same y pairs
+  __shared__ float bim[2 * NP * N];
+  __shared__ float twr[N / 4];
+  __shared__ float twi[N / 4];
+  __shared__ float win[N];
+  const int tid = threadIdx.x;
+  const int hop = p.hop[r], F = p.frames[r];
+  const int64_t row = blockIdx.y, L = p.length, Lp = L + N;
+  const int64_t q0 = (int64_t)blockIdx.x * PB;  // first padded sample owned by this workgroup
+  const float eps = p.eps;
+  st_tables<LOGN>(twr, twi, win, p.win[r]);
+  // dL/dm = c_sc (m_x - m_y) + c_log sign(log m_x - log m_y) / m_x + c_lin sign(m_x - m_y)
+  const float scale = (gloss ? gloss[0] : 1.0f) / (float)p.nres;
+  const float nd = norms[2 * r], ny = norms[2 * r + 1];
+  const float count = (float)((double)p.rows * (double)F * (double)NK);
+  const float c_sc = nd > 0.0f ? scale * p.w_sc / (nd * ny) : 0.0f;
+  const float c_log = scale * p.w_log / count, c_lin = scale * p.w_lin / count;
+  // frames t with t*h <= q0 + PB - 1 and t*h + N - 1 >= q0
+  const int64_t lo = q0 - N + 1;
+  const int t_lo = lo <= 0 ? 0 : (int)((lo + hop - 1) / hop);
+  const int t_hi = (int)((q0 + PB - 1) / hop < F - 1 ? (q0 + PB - 1) / hop : F - 1);
+  const float* xr = x + row * L;
+  const float* yr = y + row * L;
+  float acc[NACC];
+#pragma unroll
+  for (int j = 0; j < NACC; ++j) acc[j] = 0.0f;
+  __syncthreads();
+  for (int t = t_lo; t <= t_hi; t += 2 * NP) {
+    for (int i = tid; i < 2 * NP * N; i += 256) {
+      const int s = i >> LOGN, n = i & (N - 1);
+      const int ta = t + 2 * (s % NP);  // frames ta, ta + 1 of x (s < NP) or of y
+      const float* src = s < NP ? xr : yr;
+      bre[i] = ta <= t_hi ? win[n] * src[st_reflect((int64_t)ta * hop + n - N / 2, L)] : 0.0f;
+      bim[i] = ta + 1 <= t_hi ? win[n] * src[st_reflect((int64_t)(ta + 1) * hop + n - N / 2, L)] : 0.0f;
+    }
+    __syncthreads();
+    st_fft<LOGN, 2 * NP>(bre, bim, twr, twi);
+    // G of frames ta, ta + 1, and P = S_ta + i S_ta+1 (S: the Hermitian extension of G), conjugated, into the x transform;
+    // bins k and N-k are read and overwritten by the same thread
+    for (int i = tid; i < NP * NK; i += 256) {
+      const int s = i / NK, k = i - s * NK;
+      const int ta = t + 2 * s;
+      if (ta > t_hi) continue;
+      float* re = bre + s * N;
+      float* im = bim + s * N;
+      float X[2][2], Y[2][2], G[2][2];  // [frame ta / ta + 1][re, im]
+      st_split<LOGN>(re, im, k, X[0][0], X[0][1], X[1][0], X[1][1]);
+      st_split<LOGN>(bre + (NP + s) * N, bim + (NP + s) * N, k, Y[0][0], Y[0][1], Y[1][0], Y[1][1]);
+      for (int e = 0; e < 2; ++e) {
+        const float px = X[e][0] * X[e][0] + X[e][1] * X[e][1];
+        const float mx = sqrtf(fmaxf(px, eps)), my = sqrtf(fmaxf(Y[e][0] * Y[e][0] + Y[e][1] * Y[e][1], eps));
+        const float dl = logf(mx) - logf(my), dm = mx - my;
+        const float sl = (float)((dl > 0.0f) - (dl < 0.0f)), sm = (float)((dm > 0.0f) - (dm < 0.0f));
+        const float gm = c_sc * dm + c_log * sl / mx + c_lin * sm;
+        const float g = (px >= eps && ta + e <= t_hi) ? gm / mx : 0.0f;
+        G[e][0] = g * X[e][0];
+        G[e][1] = g * X[e][1];
+      }
+      if (k == 0 || k == N / 2) {
+        re[k] = G[0][0];
+        im[k] = -G[1][0];
+      } else {
+        re[k] = 0.5f * (G[0][0] - G[1][1]);
+        im[k] = -0.5f * (G[0][1] + G[1][0]);
+        re[N - k] = 0.5f * (G[0][0] + G[1][1]);
+        im[N - k] = 0.5f * (G[0][1] - G[1][0]);
+      }
+    }
+    __syncthreads();
+    // FFT(conj P) = conj(IFFT_unnormalised(P)): real part = gradient of frame ta, minus the imaginary part = of ta + 1
+    st_fft<LOGN, NP>(bre, bim, twr, twi);
+#pragma unroll
+    for (int j = 0; j < NACC; ++j) {
+      const int64_t q = q0 + tid + j * 256;
+      for (int s = 0; s < NP; ++s) {
+        const int ta = t + 2 * s;
+        const int64_t na = q - (int64_t)ta * hop, nb = na - hop;
+        if (ta <= t_hi && na >= 0 && na < N) acc[j] = fmaf(win[na], bre[s * N + na], acc[j]);
+        if (ta + 1 <= t_hi && nb >= 0 && nb < N) acc[j] = fmaf(win[nb], -bim[s * N + nb], acc[j]);
+      }
+    }
+    __syncthreads();
+  }
+  float* gp = ws + p.gp_off[r] + row * Lp;
+#pragma unroll
+  for (int j = 0; j < NACC; ++j) {
+    const int64_t q = q0 + tid + j * 256;
+    if (q < Lp) gp[q] = acc[j];
+  }
+}
+
+// dx[row, i] = sum over resolutions of the padded-row gradient at i + N/2 and at its reflect-pad mirrors
+__global__ __launch_bounds__(256) void stft_fold_kernel(const float* ws, StftPlan p, float* dx) {
+  const int64_t L = p.length;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = blockIdx.y;
+  if (i >= L) return;
+  float g = 0.0f;
+  for (int r = 0; r < p.nres; ++r) {
+    const int64_t c = p.n[r] / 2;
+    const float* gp = ws + p.gp_off[r] + row * (L + p.n[r]);
+    g += gp[i + c];
+    if (i >= 1 && i <= c) g += gp[c - i];
+    if (i >= L - 1 - c && i <= L - 2) g += gp[2 * (L - 1) - i + c];
+  }
+  dx[row * L + i] = g;
+}
+
+// validates the resolutions (N, h, W triples) and fills the plan; workspace sizes in floats
+int stft_plan(int64_t rows, int64_t length, int64_t nres, const int64_t* res, float w_sc, float w_log, float w_lin,
+              float eps, StftPlan* p, int64_t* fwd_floats, int64_t* bwd_floats) {
+  if (!res) return ADP_ERR_NULL;
+  if (nres < 1 || nres > ST_MAXR || rows < 1 || rows > 65535 || length < 2 || length >= ((int64_t)1 << 30))
+    return ADP_ERR_SHAPE;
+  p->nres = (int)nres;
+  p->rows = rows;
+  p->length = length;
+  p->w_sc = w_sc;
+  p->w_log = w_log;
+  p->w_lin = w_lin;
+  p->eps = eps;
+  int64_t fo = ST_NORMS, bo = 0;
+  for (int r = 0; r < nres; ++r) {
+    const int64_t N = res[3 * r], h = res[3 * r + 1], W = res[3 * r + 2];
+    int logn = 0;
+    while (logn < 13 && ((int64_t)1 << logn) < N) ++logn;
+    if (((int64_t)1 << logn) != N || logn < 6 || logn > 12) return ADP_ERR_UNSUPPORTED;
+    if (h < 1 || W < 1 || W > N) return ADP_ERR_UNSUPPORTED;
+    if (length <= N / 2) return ADP_ERR_SHAPE;  // reflect padding needs N/2 < L
+    const int64_t F = 1 + length / h;
+    const int64_t per_pass = N >= 512 ? 2 : 1024 / N;  // 2 * StftCfg<LOGN>::PAIRS
+    int64_t fpb = 1 + ST_SPAN_EXTRA / h;
+    if (fpb > 16 * per_pass) fpb = 16 * per_pass;
+    p->n[r] = (int)N;
+    p->logn[r] = logn;
+    p->hop[r] = (int)h;
+    p->win[r] = (int)W;
+    p->frames[r] = (int)F;
+    p->fpb[r] = (int)fpb;
+    p->chunks[r] = (int)adp_cdiv(F, fpb);
+    p->part_off[r] = fo;
+    fo += rows * p->chunks[r] * 4;
+    p->gp_off[r] = bo;
+    bo += rows * (length + N);
+  }
+  if (fwd_floats) *fwd_floats = fo;
+  if (bwd_floats) *bwd_floats = bo;
+  return ADP_OK;
+}
+
+#define ADP_STFT_DISPATCH(LAUNCH)    \
+  switch (p.logn[r]) {               \
+    case 6: LAUNCH(6); break;        \
+    case 7: LAUNCH(7); break;        \
+    case 8: LAUNCH(8); break;        \
+    case 9: LAUNCH(9); break;        \
+    case 10: LAUNCH(10); break;      \
+    case 11: LAUNCH(11); break;      \
+    default: LAUNCH(12); break;      \
+  }
+
+}  // namespace
+
+extern "C" int64_t adp_stft_loss_ws_bytes(int64_t rows, int64_t length, int64_t nres, const int64_t* res,
+                                          int64_t backward) {
+  StftPlan p;
+  int64_t f = 0, b = 0;
+  const int rc = stft_plan(rows, length, nres, res, 1.0f, 1.0f, 0.0f, 1e-8f, &p, &f, &b);
+  if (rc != ADP_OK) return rc;
+  return (backward ? b : f) * (int64_t)sizeof(float);
+}
+
+extern "C" int adp_stft_loss_fwd(const float* x, const float* y, int64_t rows, int64_t length, int64_t nres,
+                                 const int64_t* res, float w_sc, float w_log, float w_lin, float eps, float* loss,
+                                 float* ws, void* stream) {
+  if (!x || !y || !loss || !ws) return ADP_ERR_NULL;
+  StftPlan p;
+  const int rc = stft_plan(rows, length, nres, res, w_sc, w_log, w_lin, eps, &p, nullptr, nullptr);
+  if (rc != ADP_OK) return rc;
+  for (int r = 0; r < p.nres; ++r) {
+    const dim3 grid((unsigned)p.chunks[r], (unsigned)rows);
+#define ADP_STFT_FWD(LG) ADP_LAUNCH(stft_fwd_kernel<LG>, grid, dim3(256), stream, x, y, p, r, ws)
+    ADP_STFT_DISPATCH(ADP_STFT_FWD)
+#undef ADP_STFT_FWD
+  }
+  ADP_LAUNCH(stft_final_kernel, dim3(1), dim3(64), stream, ws, p, loss);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_stft_loss_bwd(const float* x, const float* y, const float* gloss, const float* ws_fwd, int64_t rows,
+                                 int64_t length, int64_t nres, const int64_t* res, float w_sc, float w_log, float w_lin,
+                                 float eps, float* dx, float* ws, void* stream) {
+  if (!x || !y || !ws_fwd || !dx || !ws) return ADP_ERR_NULL;
+  StftPlan p;
+  const int rc = stft_plan(rows, length, nres, res, w_sc, w_log, w_lin, eps, &p, nullptr, nullptr);
+  if (rc != ADP_OK) return rc;
+  for (int r = 0; r < p.nres; ++r) {
+    const int64_t pb = p.n[r] >= 1024 ? 2 * (int64_t)p.n[r] : 2048;  // StftCfg<LOGN>::PB
+    const dim3 grid((unsigned)adp_cdiv(length + p.n[r], pb), (unsigned)rows);
+#define ADP_STFT_BWD(LG) ADP_LAUNCH(stft_bwd_kernel<LG>, grid, dim3(256), stream, x, y, gloss, ws_fwd, p, r, ws)
+    ADP_STFT_DISPATCH(ADP_STFT_BWD)
+#undef ADP_STFT_BWD
+  }
+  ADP_LAUNCH(stft_fold_kernel, dim3((unsigned)adp_cdiv(length, 256), (unsigned)rows), dim3(256), stream, ws, p, dx);
+  return ADP_LAUNCH_OK();
+}

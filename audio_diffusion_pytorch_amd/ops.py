@@ -571,6 +571,34 @@ def mse_bwd(v_pred: Tensor, v_target: Tensor, gloss: Optional[Tensor]) -> Tensor
     return dv
 
 
+def _stft_res(res) -> ctypes.Array:
+    """(N, hop, win) triples -> the host int64 array adp_stft_loss_* read at the call."""
+    flat = [int(v) for triple in res for v in triple]
+    return (ctypes.c_int64 * len(flat))(*flat)
+
+
+def stft_loss_fwd(x: Tensor, y: Tensor, res, w_sc: float, w_log: float, w_lin: float, eps: float):
+    """Multi-resolution STFT loss of x against y ([..., L] rows); returns (loss, forward workspace for stft_loss_bwd)."""
+    L = x.shape[-1]
+    rows, arr = x.numel() // L, _stft_res(res)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    ws = _ws(_C.query("adp_stft_loss_ws_bytes", rows, L, len(res), arr, 0), x)
+    _C.call("adp_stft_loss_fwd", ptr(x), ptr(y), rows, L, len(res), arr, w_sc, w_log, w_lin, eps, ptr(loss), ptr(ws),
+            _C.stream())
+    return loss, ws
+
+
+def stft_loss_bwd(x: Tensor, y: Tensor, gloss: Optional[Tensor], ws_fwd: Tensor, res, w_sc: float, w_log: float,
+                  w_lin: float, eps: float) -> Tensor:
+    L = x.shape[-1]
+    rows, arr = x.numel() // L, _stft_res(res)
+    dx = torch.empty_like(x)
+    ws = _ws(_C.query("adp_stft_loss_ws_bytes", rows, L, len(res), arr, 1), x)
+    _C.call("adp_stft_loss_bwd", ptr(x), ptr(y), ptr(gloss), ptr(ws_fwd), rows, L, len(res), arr, w_sc, w_log, w_lin, eps,
+            ptr(dx), ptr(ws), _C.stream())
+    return dx
+
+
 def v_step(x: Tensor, v: Tensor, ab4: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(x)

@@ -358,6 +358,24 @@ int adp_select_rows(const float* a, const float* b, const uint8_t* pick, int64_t
 int adp_resample(const float* x, const float* kern, int64_t rows, int64_t length, int64_t fi, int64_t fo, int64_t J,
                  int64_t width, int64_t out_len, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-resolution STFT loss (losses.MultiResolutionSTFTLoss: auraloss's MultiResolutionSTFTLoss at its defaults), input x
+ * and target y of `rows` rows of `length` samples.  `res` is a HOST array of nres (<= 4) triples (fft size N: a power of two
+ * in [64, 4096]; hop >= 1; window length W <= N), read at the call (no device copy).  Per resolution: torch.stft (periodic
+ * Hann of length W centred in N, center=True, reflect padding, onesided), m = sqrt(max(|X|^2, eps)), then
+ *   w_sc ||m_y - m_x||_F / ||m_y||_F + w_log mean|log m_x - log m_y| + w_lin mean|m_x - m_y|;   loss = mean over resolutions.
+ *   adp_stft_loss_ws_bytes: workspace of the forward (backward = 0) or of the backward (backward = 1).
+ *   adp_stft_loss_fwd: loss[0]; ws keeps the per-resolution norms the backward reads (pass it as ws_fwd).
+ *   adp_stft_loss_bwd: dx = gloss[0] (1 when NULL, read on the device) * dloss/dx, the exact adjoint; y gets no gradient.
+ * Deterministic (fixed reduction orders, no atomics); R + 1 launches each way.  N/2 >= length: ADP_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------ */
+int64_t adp_stft_loss_ws_bytes(int64_t rows, int64_t length, int64_t nres, const int64_t* res, int64_t backward);
+int adp_stft_loss_fwd(const float* x, const float* y, int64_t rows, int64_t length, int64_t nres, const int64_t* res,
+                      float w_sc, float w_log, float w_lin, float eps, float* loss, float* ws, void* stream);
+int adp_stft_loss_bwd(const float* x, const float* y, const float* gloss, const float* ws_fwd, int64_t rows,
+                      int64_t length, int64_t nres, const int64_t* res, float w_sc, float w_log, float w_lin, float eps,
+                      float* dx, float* ws, void* stream);
+
 /* y = a + b (n elements); used where two gradient streams meet */
 int adp_add(const float* a, const float* b, int64_t n, float* y, void* stream);
 
