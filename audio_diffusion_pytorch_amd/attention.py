@@ -43,6 +43,9 @@ class CtxBank:
         if 8 * len(items) * M2_ * E_ > (int(os.environ.get("ADP_CTX_BANK_MAX_MB", "4096")) << 20):
             return None  # (per-item path: nothing is kept beyond an item's own backward)
         dev = context.device
+        # the tables depend on nothing but these addresses (the flat-gradient offsets are fixed by the parameter names); a graph
+        # captured over them reads them by address, so a rebuild replaces the dict and never writes into it (graphed.py and
+        # VSampler keep the dict each capture used alive)
         ptrs = tuple(t.data_ptr() for p in items for t in (p.to_kv.weight, p.norm_context.weight, p.norm_context.bias))
         cache = getattr(net, "_ctx_tables", None)
         if cache is None or cache["key"] != (dev, ptrs):

@@ -218,6 +218,15 @@ class VSampler(Sampler):
         self.schedule = schedule
         self.use_graph = use_graph
         self._graph_cache: "OrderedDict" = OrderedDict()
+        self.graph_captures = 0  # (visible to tests: steps captured / sampling runs served by replays)
+        self.graph_replays = 0
+
+    def __getstate__(self):
+        """copy.deepcopy (an EMA copy) and pickling (torch.save) leave the captured steps behind: hipGraphs can be neither
+        copied nor pickled, and a copy's graphs would read the original's weights.  The copy captures its own."""
+        state = super().__getstate__()
+        state.update(_graph_cache=OrderedDict(), graph_captures=0, graph_replays=0)
+        return state
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
         angle = sigmas * pi / 2
@@ -278,15 +287,22 @@ class VSampler(Sampler):
         is (x shape, kwarg names, tensor shapes/dtypes, python scalar values); the entry owns static copies of every
         tensor kwarg (also those nested in `channels`) and the caller's tensors are copied into them before the
         replays, so fresh conditioning tensors per call reuse the graph and can never be read after they are freed.
+        An entry is recaptured when a parameter of the net moved or was replaced (the graph holds their addresses), and it
+        keeps the context-bank tables it was captured with alive (graphed.ctx_tables_under).
         Per step only two tiny device-to-device copies (sigma row, alpha/beta row) precede the replay.  Returns None
         (eager fallback) for kwargs that cannot be made static."""
+        from .graphed import ctx_tables_under, param_signature, tracked_parameters
         names = sorted(kwargs)
         live: List[Tensor] = []
         specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
         if any(sp is None for _, sp in specs) or any(not t.is_cuda for t in live):
             return None
         key = (tuple(x.shape), x.device, specs, cond is not None)
+        psig = param_signature(tracked_parameters(self.net))
         entry = self._graph_cache.get(key)
+        if entry is not None and entry[6] != psig:  # stale parameter addresses: drop the graph, never replay it
+            del self._graph_cache[key]
+            entry = None
         if entry is None:
             sx, ssig, sab = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(ab[0])
             scond = torch.empty_like(cond[0]) if cond is not None else None  # this step's rows of the hoisted conditioning
@@ -311,13 +327,15 @@ class VSampler(Sampler):
             with torch.cuda.graph(graph):
                 v = self.net(sx, ssig, **skw)
                 ops.v_step(sx, v.contiguous(), sab, out=sx)  # in place: each element is read then written
-            entry = (graph, sx, ssig, sab, statics, scond)
+            entry = (graph, sx, ssig, sab, statics, scond, psig, ctx_tables_under(self.net))
             self._graph_cache[key] = entry
+            self.graph_captures += 1
             while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
                 self._graph_cache.popitem(last=False)  # least recently used graph + its buffers
         else:
             self._graph_cache.move_to_end(key)
-        graph, sx, ssig, sab, statics, scond = entry
+        self.graph_replays += 1
+        graph, sx, ssig, sab, statics, scond = entry[:6]
         sx.copy_(x)
         for st, t in zip(statics, live):
             st.copy_(t)

@@ -17,8 +17,16 @@ eager step.  What is captured is exactly the eager path (`VDiffusion._forward_ea
 Taken only where it is safe, else the eager step runs as before (never an error): CUDA tensors, grad mode on, the stock
 `UniformDistribution`, inputs / conditioning tensors that do not require grad, keyword arguments that can be made static
 (tensors, None, python scalars, lists of those), no data-parallel hook on the U-Net (its collectives are captured explicitly
-by parallel.capture_step), not already inside a stream capture.  `VDiffusion(use_graph=False)` or ADP_TRAIN_GRAPH=0 switch it
-off.  A capture that fails (e.g. a user loss_fn that syncs with the host) marks its call structure as eager-only.
+by parallel.capture_step), not already inside a stream capture, and no replayed loss of the same call structure still waiting
+for its backward (`(model(x1) + model(x2)).backward()`, or a stray forward between `loss = model(x)` and `loss.backward()`:
+the replayed step keeps ONE set of activations, so the second forward runs eagerly; replays resume once the pending loss is
+backpropagated or dropped).  `VDiffusion(use_graph=False)` or ADP_TRAIN_GRAPH=0 switch it off.  A capture that fails (e.g. a
+user loss_fn that syncs with the host) marks its call structure as eager-only.
+
+What a capture bakes in: the parameters' addresses (an entry is recaptured when one moves or is replaced), the `loss_fn`
+object and the `UniformDistribution`'s (vmin, vmax) (both part of the cache key), and the context-bank pointer tables of the
+nets under the module (attention.CtxBank; every entry keeps the tables it was captured with alive).  Any other Python-side
+state that a custom `net_t` reads in its forward is frozen at capture time as well.
 """
 import os
 import weakref
@@ -79,9 +87,29 @@ def tracked_parameters(module: nn.Module) -> List[nn.Parameter]:
     return params
 
 
+def param_signature(params) -> tuple:
+    """What a captured graph assumes about the parameters: their addresses and whether they are differentiated."""
+    return tuple((p.data_ptr(), p.requires_grad) for p in params)
+
+
+def ctx_tables_under(module: nn.Module) -> list:
+    """The context-bank pointer tables (attention.CtxBank) of every net under `module`.  A graph captured over such a net reads
+    them by address, so every captured entry holds the ones it was captured with: a net rebuilds its tables when its
+    parameters move, and the old ones must outlive every graph that still points at them."""
+    return [t for m in module.modules() if (t := m.__dict__.get("_ctx_tables")) is not None]
+
+
+class _Pending:
+    """Lives on the autograd node of a replayed loss until that node's backward runs or the loss is dropped."""
+    __slots__ = ("__weakref__",)
+
+
 class _Entry:
-    """One captured call structure: static inputs, the two graphs, the static loss / incoming gradient / parameter gradients."""
-    __slots__ = ("g_f", "g_b", "sx", "snoise", "statics", "sloss", "sgloss", "params", "grads", "sig", "step")
+    """One captured call structure: static inputs, the two graphs, the static loss / incoming gradient / parameter gradients;
+    `keep` holds what the graphs read without owning it (loss_fn, context-bank tables), `pending` a weak reference to the
+    _Pending token of the last replayed loss."""
+    __slots__ = ("g_f", "g_b", "sx", "snoise", "statics", "sloss", "sgloss", "params", "grads", "sig", "step", "keep",
+                 "pending")
 
 
 class _Replay(torch.autograd.Function):
@@ -92,12 +120,15 @@ class _Replay(torch.autograd.Function):
         entry.g_f.replay()
         entry.step += 1
         ctx.entry, ctx.step = entry, entry.step
+        ctx.token = _Pending()
+        entry.pending = weakref.ref(ctx.token)
         return entry.sloss.clone()
 
     @staticmethod
     def backward(ctx, gloss):
         entry: _Entry = ctx.entry
-        if ctx.step != entry.step:
+        ctx.token = None  # (this loss no longer needs the activations: the next forward may replay again)
+        if ctx.step != entry.step:  # (reachable with retain_graph=True only: a second backward after a later replay)
             raise RuntimeError("graph-replayed training step: backward() of a loss whose forward is no longer the last one run "
                                "at this shape (the replayed step keeps ONE set of activations); call backward before the next "
                                "forward, or construct the diffusion with use_graph=False / set ADP_TRAIN_GRAPH=0")
@@ -115,19 +146,17 @@ class _Replay(torch.autograd.Function):
 
 class TrainStepGraphs:
     """Cache of captured training steps of one diffusion module, keyed on the call STRUCTURE (shapes, kwarg names, tensor
-    shapes / dtypes, python scalar values -- never object identity), LRU-bounded: every entry owns its activations."""
+    shapes / dtypes, python scalar values -- never the identity of an input) and on the module's loss_fn and sigma bounds,
+    LRU-bounded: every entry owns its activations."""
 
     MAX_ENTRIES = 2
 
     def __init__(self, owner: nn.Module):
         self._owner = weakref.ref(owner)  # (the registry below is keyed weakly on the owner: no cycle through this object)
         self.cache: "OrderedDict[Any, _Entry]" = OrderedDict()
-        self.eager_only = set()
+        self.eager_only: Dict[Any, Any] = {}  # key -> its loss_fn (held: the key names it by id)
         self.captures = 0  # (visible to tests / bench: how many times a step was captured)
         self.replays = 0
-
-    def _signature(self, params):
-        return tuple((p.data_ptr(), p.requires_grad) for p in params)
 
     def run(self, x: Tensor, noise: Optional[Tensor], kwargs: Dict[str, Any]) -> Optional[Tensor]:
         from .diffusion import _kw_spec
@@ -136,21 +165,26 @@ class TrainStepGraphs:
         specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
         if any(sp is None for _, sp in specs) or any((not t.is_cuda) or t.requires_grad for t in live):
             return None
-        key = (tuple(x.shape), x.dtype, x.device, noise is not None, specs)
+        owner = self._owner()
+        loss_fn, dist = owner.loss_fn, owner.sigma_distribution
+        # (the captured step calls this loss_fn and draws sigmas from these bounds; the entry holds loss_fn, so its id is unique)
+        key = (tuple(x.shape), x.dtype, x.device, noise is not None, specs, id(loss_fn), dist.vmin, dist.vmax)
         if key in self.eager_only:
             return None
-        all_params = tracked_parameters(self._owner())
-        sig = self._signature(all_params)
+        all_params = tracked_parameters(owner)
+        sig = param_signature(all_params)
         entry = self.cache.get(key)
         if entry is not None and entry.sig != sig:  # parameters moved / replaced / (un)frozen: the graph holds stale pointers
             del self.cache[key]
             entry = None
+        if entry is not None and entry.pending is not None and entry.pending() is not None:
+            return None  # a replayed loss of this entry still waits for its backward, which needs the activations: run eagerly
         if entry is None:
             params = [p for p in all_params if p.requires_grad]
             if not params:
                 return None
             try:
-                with _ProxyParameters(self._owner()) as proxies:
+                with _ProxyParameters(owner) as proxies:
                     entry = self._capture(x, noise, kwargs, names, live, [q for q in proxies if q.requires_grad])
                 entry.params = params
                 del proxies
@@ -158,10 +192,12 @@ class TrainStepGraphs:
                 import warnings
                 warnings.warn(f"graph capture of the training step failed ({type(e).__name__}: {e}); this call structure runs "
                               f"eagerly from now on", RuntimeWarning)
-                self.eager_only.add(key)
+                self.eager_only[key] = loss_fn
                 torch.cuda.synchronize(x.device)
                 return None
             entry.sig = sig
+            entry.keep = (loss_fn, ctx_tables_under(owner))
+            entry.pending = None
             self.cache[key] = entry
             while len(self.cache) > self.MAX_ENTRIES:
                 self.cache.popitem(last=False)

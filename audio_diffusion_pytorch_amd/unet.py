@@ -376,7 +376,9 @@ class UNetV0Net(nn.Module):
             self._named_cache, self._named_holders = cached, holders
             self._pname_cache = {id(p): n for n, p in cached}
             self._named_cache_of = id(self)
-            self._ctx_tables = None  # (pointer tables of the cross-attention context bank: rebuilt from the new objects)
+            # (the context bank's pointer tables are NOT dropped here: they are keyed on the parameters' addresses and rebuilt
+            #  when those change; a rebuild of this cache alone -- after a capture under graphed._ProxyParameters -- leaves the
+            #  addresses, and the tables that captured graphs read, as they are)
         return cached
 
     def _param_offsets(self):

@@ -65,7 +65,7 @@ def test_readme_loop_replays_and_matches_the_eager_step(hip):
 
 
 @pytest.mark.gpu
-def test_replayed_step_keeps_autograd_semantics(hip):
+def test_replayed_step_matches_eager_autograd_semantics(hip):
     m = _model(hip)
     x, noise = torch.randn(2, 2, 4096, device=hip), torch.randn(2, 2, 4096, device=hip)
     ref = _model(hip, diffusion_use_graph=False)
@@ -93,13 +93,34 @@ def test_replayed_step_keeps_autograd_semantics(hip):
     m(x).backward()
     h.remove()
     assert len(seen) == 1 and seen[0] > 0
-    # a stale forward is refused instead of silently differentiating the wrong activations
+    # a second forward while a replayed loss waits for its backward runs eagerly (the replayed step keeps ONE set of
+    # activations): the pending loss differentiates its own activations, exactly as in the eager step
+    g = graphed.GRAPHS_OF[m.diffusion]
+    r0 = g.replays
+    stray = []
+    for model in (m, ref):
+        _zero(model)
+        torch.manual_seed(8)
+        torch.cuda.manual_seed(8)
+        l1 = model(x)
+        model(x)
+        l1.backward()
+        stray.append([p.grad.clone() for p in model.parameters()])
+    for a, b in zip(*stray):
+        assert torch.equal(a, b)
+    assert g.replays == r0 + 1, "the first forward replayed, the second ran eagerly"
+    # a stale backward is still refused instead of silently differentiating the wrong activations: after a
+    # backward(retain_graph=True) the next forward replays again, and a second backward of the old loss would read the newer
+    # step's activations
+    _zero(m)
     l1 = m(x)
+    l1.backward(retain_graph=True)
     m(x)
+    assert g.replays == r0 + 3
     with pytest.raises(RuntimeError, match="no longer the last one"):
         l1.backward()
+    del l1
     # no_grad / CPU-side validation loops stay eager and leave the graphs alone
-    g = graphed.GRAPHS_OF[m.diffusion]
     n = g.replays
     with torch.no_grad():
         m(x)
