@@ -14,6 +14,7 @@ from .diffusion import (
 )
 from .losses import MultiResolutionSTFTLoss, STFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
+from .optim import AdamW
 from .unet import UNetV0Net
 
 XUNet = UNetV0Net
@@ -43,5 +44,5 @@ __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
     "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "DiffusionModel", "DiffusionUpsampler",
     "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
-    "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss",
+    "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
 ]

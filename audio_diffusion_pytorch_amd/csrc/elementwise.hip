@@ -200,6 +200,200 @@ __global__ __launch_bounds__(256) void fourier_bwd_kernel(const float* t, const 
   dw[h] = accumulate ? dw[h] + s : s;
 }
 
+// ---- fused AdamW step (optim.AdamW): gradient clipping at load, decoupled weight decay, moments, update, EMA lerp.
+// Work is cut into chunks [tensor, first element, count] by the host (a 1 M-element conv weight and an 8-element bias
+// balance); blocks stride over the chunk table.  Per chunk: scalar head up to the first 16-byte boundary of p, 16-byte
+// accesses on the interior (two groups per lane in flight: ten independent loads before the first use), scalar tail.
+// Gradients are slices of the flat gradient buffer, aligned to 4 bytes only: they are read through ld4_unaligned.
+constexpr int OPT_MAX_PARTIALS = 1024;
+
+// The tensors' addresses come out of a device table, so the compiler cannot tell that they are global memory and would use
+// flat_ accesses (which also pass through the LDS aperture check and count on lgkmcnt): say so.
+#ifdef ADP_EMULATE
+#define OPT_GLOBAL
+#else
+#define OPT_GLOBAL __attribute__((address_space(1)))
+#endif
+typedef f32x4 f32x4_a4 __attribute__((aligned(4)));
+__device__ __forceinline__ float opt_ld(const float* p) { return *(const OPT_GLOBAL float*)p; }
+__device__ __forceinline__ void opt_st(float* p, float v) { *(OPT_GLOBAL float*)p = v; }
+__device__ __forceinline__ f32x4 opt_ld4(const float* p) { return *(const OPT_GLOBAL f32x4*)p; }
+__device__ __forceinline__ void opt_st4(float* p, f32x4 v) { *(OPT_GLOBAL f32x4*)p = v; }
+// 4-byte aligned address: the compiler picks the widest load the target allows (global_load_dwordx4 on gfx950)
+__device__ __forceinline__ f32x4 ld4_unaligned(const float* p) { return *(const OPT_GLOBAL f32x4_a4*)p; }
+
+__device__ __forceinline__ int64_t opt_head(const void* p, int64_t cnt) {
+  const int64_t h = (int64_t)((16 - ((uintptr_t)p & 15)) & 15) >> 2;  // elements up to the next 16-byte boundary
+  return h < cnt ? h : cnt;
+}
+
+// block-wide sum of one double per thread in a fixed order (no 8-byte shuffles: an LDS tree); all threads get the result
+__device__ __forceinline__ double opt_block_sum(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__device__ __forceinline__ double opt_sq(double acc, float g) { return fma((double)g, (double)g, acc); }
+__device__ __forceinline__ double opt_sq4(double acc, f32x4 g) {
+  return opt_sq(opt_sq(opt_sq(opt_sq(acc, g[0]), g[1]), g[2]), g[3]);
+}
+
+__global__ __launch_bounds__(256) void sqnorm_partials_kernel(const float* const* ptrs, const int64_t* numels,
+                                                              const int64_t* chunks, int64_t n_chunks,
+                                                              double* partials) {
+  __shared__ double sh[256];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t t = chunks[3 * c], start = chunks[3 * c + 1];
+    int64_t cnt = chunks[3 * c + 2];
+    if (start + cnt > numels[t]) cnt = numels[t] - start;  // (a table that disagrees with the tensors never reads past them)
+    if (cnt <= 0) continue;
+    const float* g = ptrs[t] + start;
+    const int64_t head = opt_head(g, cnt);
+    if (tid < head) acc = opt_sq(acc, opt_ld(g + tid));
+    const int64_t nv = (cnt - head) & ~(int64_t)3;
+    const float* gv = g + head;
+    for (int64_t i = 4 * (int64_t)tid; i < nv; i += 2048) {
+      const bool two = i + 1024 < nv;
+      const f32x4 a = opt_ld4(gv + i);
+      f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (two) b = opt_ld4(gv + i + 1024);
+      acc = opt_sq4(opt_sq4(acc, a), b);
+    }
+    const int64_t j = head + nv + tid;
+    if (j < cnt) acc = opt_sq(acc, opt_ld(g + j));
+  }
+  acc = opt_block_sum(acc, sh);
+  if (tid == 0) partials[blockIdx.x] = acc;
+}
+
+struct AdamwScalars {
+  float decay;         // 1 - lr * weight_decay
+  float one_m_beta1;   // 1 - beta1
+  float beta2;
+  float one_m_beta2;   // 1 - beta2
+  float inv_bc2_sqrt;  // 1 / sqrt(1 - beta2^step)
+  float eps;
+  float step_size;     // lr / (1 - beta1^step)
+  float ema_w;         // 1 - ema_decay
+};
+
+// one element: every multiply-add is spelled fmaf and the compiler may not form others (it would fuse g * clip into the
+// subtraction below in one path and not in the other), so the scalar and the 16-byte paths (and the emulated build) round alike
+__device__ __forceinline__ void adamw_elem(const AdamwScalars& s, float clip, float& p, float g, float& m, float& v) {
+#pragma clang fp contract(off)
+  g *= clip;
+  m = fmaf(g - m, s.one_m_beta1, m);
+  v = fmaf(g * s.one_m_beta2, g, v * s.beta2);
+  const float denom = fmaf(sqrtf(v), s.inv_bc2_sqrt, s.eps);
+  p = fmaf(-s.step_size, m / denom, p * s.decay);
+}
+
+template <bool EMA>
+__device__ __forceinline__ void adamw_scalar_at(const AdamwScalars& s, float clip, const adp_adamw_tensor& T, int64_t i) {
+  float p = opt_ld(T.p + i), m = opt_ld(T.m + i), v = opt_ld(T.v + i);
+  adamw_elem(s, clip, p, opt_ld(T.g + i), m, v);
+  opt_st(T.p + i, p);
+  opt_st(T.m + i, m);
+  opt_st(T.v + i, v);
+  if (EMA) {
+    const float e = opt_ld(T.ema + i);
+    opt_st(T.ema + i, fmaf(p - e, s.ema_w, e));
+  }
+}
+
+template <bool EMA>
+struct AdamwGroup4 {
+  f32x4 p, g, m, v, e;
+  __device__ __forceinline__ void load(const adp_adamw_tensor& T, int64_t i) {
+    p = opt_ld4(T.p + i);
+    g = ld4_unaligned(T.g + i);
+    m = opt_ld4(T.m + i);
+    v = opt_ld4(T.v + i);
+    if (EMA) e = opt_ld4(T.ema + i);
+  }
+  __device__ __forceinline__ void update_store(const AdamwScalars& s, float clip, const adp_adamw_tensor& T, int64_t i) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = p[k], mk = m[k], vk = v[k];
+      adamw_elem(s, clip, pk, g[k], mk, vk);
+      p[k] = pk;
+      m[k] = mk;
+      v[k] = vk;
+      if (EMA) e[k] = fmaf(pk - e[k], s.ema_w, e[k]);
+    }
+    opt_st4(T.p + i, p);
+    opt_st4(T.m + i, m);
+    opt_st4(T.v + i, v);
+    if (EMA) opt_st4(T.ema + i, e);
+  }
+};
+
+template <bool EMA>
+__device__ __forceinline__ void adamw_chunk(const AdamwScalars& s, float clip, const adp_adamw_tensor& T, int64_t cnt) {
+  const int tid = threadIdx.x;
+  // m, v (and the EMA tensor) must share p's 16-byte phase for the 16-byte path; allocations of their own always do
+  uintptr_t phase = ((uintptr_t)T.p ^ (uintptr_t)T.m) | ((uintptr_t)T.p ^ (uintptr_t)T.v);
+  if (EMA) phase |= (uintptr_t)T.p ^ (uintptr_t)T.ema;
+  if (phase & 15) {
+    for (int64_t i = tid; i < cnt; i += 256) adamw_scalar_at<EMA>(s, clip, T, i);
+    return;
+  }
+  const int64_t head = opt_head(T.p, cnt);
+  if (tid < head) adamw_scalar_at<EMA>(s, clip, T, tid);
+  const int64_t nv = (cnt - head) & ~(int64_t)3;
+  for (int64_t i = head + 4 * (int64_t)tid; i < head + nv; i += 2048) {
+    const bool two = i + 1024 < head + nv;
+    AdamwGroup4<EMA> a, b;
+    a.load(T, i);
+    if (two) b.load(T, i + 1024);
+    a.update_store(s, clip, T, i);
+    if (two) b.update_store(s, clip, T, i + 1024);
+  }
+  const int64_t j = head + nv + tid;
+  if (j < cnt) adamw_scalar_at<EMA>(s, clip, T, j);
+}
+
+__global__ __launch_bounds__(256) void adamw_step_kernel(const adp_adamw_tensor* tensors, const int64_t* chunks,
+                                                         int64_t n_chunks, AdamwScalars s, const double* partials,
+                                                         int n_partials, float max_grad_norm, float* grad_norm_out) {
+  __shared__ double sh[256];
+  float clip = 1.0f;
+  if (partials) {
+    // every block adds the (at most 1024, L2-resident) partials in the same fixed order: one coefficient, no third launch
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
+    const float norm = (float)sqrt(opt_block_sum(acc, sh));
+    const float c = max_grad_norm / (norm + 1e-6f);
+    clip = c > 1.0f ? 1.0f : c;  // (a NaN norm stays a NaN coefficient, as torch.clamp(max=1) keeps it)
+    if (grad_norm_out && blockIdx.x == 0 && threadIdx.x == 0) grad_norm_out[0] = norm;
+  }
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t t = chunks[3 * c], start = chunks[3 * c + 1];
+    int64_t cnt = chunks[3 * c + 2];
+    adp_adamw_tensor T = tensors[t];
+    if (start + cnt > T.numel) cnt = T.numel - start;
+    if (cnt <= 0) continue;
+    T.p += start;
+    T.g += start;
+    T.m += start;
+    T.v += start;
+    if (T.ema) {
+      T.ema += start;
+      adamw_chunk<true>(s, clip, T, cnt);
+    } else {
+      adamw_chunk<false>(s, clip, T, cnt);
+    }
+  }
+}
+
 unsigned stream_grid(int64_t n) {
   int64_t g = adp_cdiv(n, 256 * 4);
   if (g > 4096) g = 4096;
@@ -427,5 +621,28 @@ extern "C" int adp_time_fourier_bwd(const float* t, const float* w, const float*
   if (B <= 0 || H <= 0) return ADP_ERR_SHAPE;
   ADP_LAUNCH(fourier_bwd_kernel, dim3((unsigned)adp_cdiv(H, 256)), dim3(256), stream, t, w, dfour, B, H,
              (int)accumulate, dw);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int64_t adp_sqnorm_partials(const float* const* ptrs, const int64_t* numels, int64_t n_tensors,
+                                       const int64_t* chunk_table, int64_t n_chunks, double* partials, void* stream) {
+  if (!ptrs || !numels || !chunk_table || !partials) return ADP_ERR_NULL;
+  if (n_tensors <= 0 || n_chunks <= 0) return ADP_ERR_SHAPE;
+  const int64_t nb = n_chunks < OPT_MAX_PARTIALS ? n_chunks : OPT_MAX_PARTIALS;
+  ADP_LAUNCH(sqnorm_partials_kernel, dim3((unsigned)nb), dim3(256), stream, ptrs, numels, chunk_table, n_chunks,
+             partials);
+  return ADP_LAUNCH_OK() == ADP_OK ? nb : ADP_ERR_LAUNCH;
+}
+
+extern "C" int adp_adamw_step(const adp_adamw_tensor* tensors, const int64_t* chunk_table, int64_t n_chunks, float decay,
+                              float one_minus_beta1, float beta2, float one_minus_beta2, float inv_bc2_sqrt, float eps,
+                              float step_size, float ema_weight, const double* partials, int64_t n_partials,
+                              float max_grad_norm, float* grad_norm_out, void* stream) {
+  if (!tensors || !chunk_table) return ADP_ERR_NULL;
+  if (n_chunks <= 0 || (partials && (n_partials <= 0 || n_partials > OPT_MAX_PARTIALS))) return ADP_ERR_SHAPE;
+  const AdamwScalars s{decay, one_minus_beta1, beta2, one_minus_beta2, inv_bc2_sqrt, eps, step_size, ema_weight};
+  const int64_t nb = n_chunks < 4096 ? n_chunks : 4096;
+  ADP_LAUNCH(adamw_step_kernel, dim3((unsigned)nb), dim3(256), stream, tensors, chunk_table, n_chunks, s, partials,
+             (int)n_partials, max_grad_norm, grad_norm_out);
   return ADP_LAUNCH_OK();
 }

@@ -658,6 +658,25 @@ def axpby(a: float, x: Tensor, b: float = 0.0, y: Optional[Tensor] = None, out: 
     return out
 
 
+def sqnorm_partials(ptrs: Tensor, numels: Tensor, chunks: Tensor, partials: Tensor) -> int:
+    """Per-block sums of squares (double) of the gradients named by the device tables (adp_sqnorm_partials): ptrs / numels
+    int64 [T], chunks int64 [C, 3] = (tensor, first element, count); returns how many entries of `partials` were written."""
+    assert partials.numel() >= 1024, "sqnorm_partials: the partials buffer holds one double per block (up to 1024)"
+    return _C.call_value("adp_sqnorm_partials", ptr(ptrs, torch.int64), ptr(numels, torch.int64), ptrs.numel(),
+                         ptr(chunks, torch.int64), chunks.shape[0], ptr(partials, torch.float64), _C.stream())
+
+
+def adamw_step(tensors: Tensor, chunks: Tensor, *, decay: float, one_minus_beta1: float, beta2: float,
+               one_minus_beta2: float, inv_bc2_sqrt: float, eps: float, step_size: float, ema_weight: float = 0.0,
+               partials: Optional[Tensor] = None, n_partials: int = 0, max_grad_norm: float = 0.0,
+               grad_norm_out: Optional[Tensor] = None) -> None:
+    """One fused AdamW launch (adp_adamw_step) over the chunks of a device table: tensors int64 [T, 6] = (p, g, m, v, ema or 0,
+    numel), chunks int64 [C, 3].  The scalars are the host's doubles; `partials` (from sqnorm_partials) switches clipping on."""
+    _C.call("adp_adamw_step", ptr(tensors, torch.int64), ptr(chunks, torch.int64), chunks.shape[0], decay, one_minus_beta1,
+            beta2, one_minus_beta2, inv_bc2_sqrt, eps, step_size, ema_weight, ptr(partials, torch.float64), n_partials,
+            max_grad_norm, ptr(grad_norm_out), _C.stream())
+
+
 def concat_channels(x: Tensor, x2: Tensor) -> Tensor:
     """torch.cat([x, x2], dim=1) of [B, C, L] tensors as two strided row copies (adp_copy2d)."""
     B, C1, L = x.shape

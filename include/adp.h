@@ -376,6 +376,37 @@ int adp_stft_loss_bwd(const float* x, const float* y, const float* gloss, const 
                       int64_t length, int64_t nres, const int64_t* res, float w_sc, float w_log, float w_lin, float eps,
                       float* dx, float* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused AdamW step (optim.AdamW: torch.optim.AdamW + clip_grad_norm_(norm_type=2) + an EMA copy of the weights).
+ * Both launches walk a DEVICE chunk table of int64 triples [tensor index, first element, count] that the host builds once
+ * (fixed-size chunks, so a 1 M-element weight and an 8-element bias balance); blocks stride over it.  Tensors are fp32,
+ * aligned to 4 bytes (16-byte accesses are used where the addresses allow); a chunk is clipped to its tensor's numel.
+ *   sqnorm partials: ptrs / numels are DEVICE arrays of n_tensors gradient pointers / lengths (consecutive slices of one
+ *     buffer may be described as one tensor).  One launch on min(n_chunks, 1024) blocks; block b writes the sum of squares of
+ *     its chunks, accumulated in double, to partials[b].  Returns the number of partials written (negative: error code).
+ *   adamw step: `tensors` is a DEVICE array of adp_adamw_tensor records; ema NULL: no EMA tensor.  With g' = clip * g,
+ *       p <- p * decay;  m <- m + (g' - m) * one_minus_beta1;  v <- v * beta2 + one_minus_beta2 * g'^2;
+ *       p <- p - step_size * m / (sqrt(v) * inv_bc2_sqrt + eps);  ema <- ema + ema_weight * (p - ema)
+ *     (decay = 1 - lr * weight_decay, step_size = lr / (1 - beta1^step), inv_bc2_sqrt = (1 - beta2^step)^-1/2: host doubles
+ *     rounded to float).  partials NULL: clip = 1.  Otherwise every block adds partials[0 .. n_partials) (<= 1024) in one
+ *     fixed order, norm = sqrt(sum), clip = min(1, max_grad_norm / (norm + 1e-6)), and block 0 writes norm to grad_norm_out
+ *     (may be NULL).  g is read only.  Deterministic, no atomics; one launch each.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  float* ema;
+  int64_t numel;
+} adp_adamw_tensor;
+int64_t adp_sqnorm_partials(const float* const* ptrs, const int64_t* numels, int64_t n_tensors, const int64_t* chunk_table,
+                            int64_t n_chunks, double* partials, void* stream);
+int adp_adamw_step(const adp_adamw_tensor* tensors, const int64_t* chunk_table, int64_t n_chunks, float decay,
+                   float one_minus_beta1, float beta2, float one_minus_beta2, float inv_bc2_sqrt, float eps,
+                   float step_size, float ema_weight, const double* partials, int64_t n_partials, float max_grad_norm,
+                   float* grad_norm_out, void* stream);
+
 /* y = a + b (n elements); used where two gradient streams meet */
 int adp_add(const float* a, const float* b, int64_t n, float* y, void* stream);
 
