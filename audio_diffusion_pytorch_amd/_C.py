@@ -91,6 +91,7 @@ SIGNATURES = {
     "adp_mse_fwd": (c_int, [P, P, I, P, P, P]),
     "adp_mse_bwd": (c_int, [P, P, P, I, P, P]),
     "adp_v_step": (c_int, [P, P, P, I, P, P]),
+    "adp_v_step2": (c_int, [P, P, P, P, P, I, P, P, P, P]),
     "adp_sqnorm_partials": (I, [P, P, I, P, I, P, P]),
     "adp_adamw_step": (c_int, [P, P, I, F, F, F, F, F, F, F, F, P, I, F, P, P]),
     "adp_add": (c_int, [P, P, I, P, P]),

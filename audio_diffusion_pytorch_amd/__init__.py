@@ -10,6 +10,7 @@ from .diffusion import (
     UniformDistribution,
     VDiffusion,
     VInpainter,
+    VMultistepSampler,
     VSampler,
 )
 from .losses import MultiResolutionSTFTLoss, STFTLoss
@@ -42,7 +43,7 @@ def LTPlugin(*args, **kwargs):
 
 __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
-    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "DiffusionModel", "DiffusionUpsampler",
-    "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
+    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "DiffusionModel",
+    "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
 ]

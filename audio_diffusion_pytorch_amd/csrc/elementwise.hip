@@ -2,6 +2,7 @@
 //   adp_v_noise  : diffusion.py:88-92   x_noisy = a x + b n ; v_target = a n - b x      (2 reads, 2 writes)
 //   adp_mse_*    : diffusion.py:95      F.mse_loss(v_pred, v_target) and its gradient
 //   adp_v_step   : diffusion.py:185-187 one VSampler update, 2 reads 1 write
+//   adp_v_step2  : one VMultistepSampler update (two-step exponential integrator), 4 reads 3 writes
 //   adp_time_fourier_* : a_unet NumberEmbedder under TimeConditioningPlugin (components.py:74-76)
 #include "adp_rt.h"
 #ifndef ADP_EMULATE
@@ -70,6 +71,79 @@ __global__ __launch_bounds__(256) void v_step_kernel(const float* x, const float
     const float n_pred = b0 * xv + a0 * vv;
     xo[i] = a1 * x_pred + b1 * n_pred;
   }
+}
+
+// one VMultistepSampler update (second-order two-step exponential integrator in the angle phi = sigma * pi / 2):
+//   x0 = a0 x - b0 v ; eps = b0 x + a0 v
+//   x_next = a1 x0 + b1 eps + ca (x0 - x0_prev) + cb (eps - eps_prev) ; history <- (x0, eps)
+// coef6 = device [a0, b0, a1, b1, ca, cb].  A row with ca = cb = 0 (the first step) does NOT read the history: whatever an
+// earlier run or the allocator left there (NaN included) cannot reach x.  Every output may alias its input: an element is
+// read, then written, by the one lane that owns it.
+struct VStep2Coef {
+  float a0, b0, a1, b1, ca, cb;
+};
+
+template <bool HIST>
+__device__ __forceinline__ float v_step2_elem(const VStep2Coef& c, float xv, float vv, float& hx, float& he) {
+  const float x_pred = c.a0 * xv - c.b0 * vv;
+  const float n_pred = c.b0 * xv + c.a0 * vv;
+  float xn = c.a1 * x_pred + c.b1 * n_pred;
+  if (HIST) xn += c.ca * (x_pred - hx) + c.cb * (n_pred - he);
+  hx = x_pred;
+  he = n_pred;
+  return xn;
+}
+
+template <bool HIST>
+__device__ __forceinline__ void v_step2_scalar_at(const VStep2Coef& c, const float* x, const float* v, const float* hx,
+                                                  const float* he, int64_t i, float* xo, float* hxo, float* heo) {
+  float px = 0.0f, pe = 0.0f;
+  if (HIST) {
+    px = hx[i];
+    pe = he[i];
+  }
+  const float xn = v_step2_elem<HIST>(c, x[i], v[i], px, pe);
+  xo[i] = xn;
+  hxo[i] = px;
+  heo[i] = pe;
+}
+
+// VEC: all seven pointers are 16-byte aligned -> 16-byte accesses on the first n & ~3 elements, scalar tail behind them
+template <bool HIST, bool VEC>
+__device__ __forceinline__ void v_step2_body(const VStep2Coef& c, const float* x, const float* v, const float* hx,
+                                             const float* he, int64_t n, float* xo, float* hxo, float* heo) {
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthreads = (int64_t)gridDim.x * 256;
+  const int64_t nv = VEC ? (n & ~(int64_t)3) : 0;
+  for (int64_t i = 4 * tid; i < nv; i += 4 * nthreads) {
+    const f32x4 xv = *(const f32x4*)(x + i), vv = *(const f32x4*)(v + i);
+    f32x4 px = {0.0f, 0.0f, 0.0f, 0.0f}, pe = {0.0f, 0.0f, 0.0f, 0.0f}, xn;
+    if (HIST) {
+      px = *(const f32x4*)(hx + i);
+      pe = *(const f32x4*)(he + i);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pxk = px[k], pek = pe[k];
+      xn[k] = v_step2_elem<HIST>(c, xv[k], vv[k], pxk, pek);
+      px[k] = pxk;
+      pe[k] = pek;
+    }
+    *(f32x4*)(xo + i) = xn;
+    *(f32x4*)(hxo + i) = px;
+    *(f32x4*)(heo + i) = pe;
+  }
+  for (int64_t i = nv + tid; i < n; i += nthreads) v_step2_scalar_at<HIST>(c, x, v, hx, he, i, xo, hxo, heo);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void v_step2_kernel(const float* x, const float* v, const float* hx, const float* he,
+                                                      const float* coef6, int64_t n, float* xo, float* hxo,
+                                                      float* heo) {
+  const VStep2Coef c{coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
+  if (c.ca == 0.0f && c.cb == 0.0f)  // (the same branch in every lane of the launch)
+    v_step2_body<false, VEC>(c, x, v, hx, he, n, xo, hxo, heo);
+  else
+    v_step2_body<true, VEC>(c, x, v, hx, he, n, xo, hxo, heo);
 }
 
 // one VInpainter resample step (diffusion.py:339-350): rotate (x, v) from noise level i to level j, re-noise the
@@ -528,6 +602,22 @@ extern "C" int adp_v_step(const float* x, const float* v, const float* ab4, int6
   if (!x || !v || !ab4 || !x_out) return ADP_ERR_NULL;
   if (n <= 0) return ADP_ERR_SHAPE;
   ADP_LAUNCH(v_step_kernel, dim3(stream_grid(n)), dim3(256), stream, x, v, ab4, n, x_out);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_v_step2(const float* x, const float* v, const float* hist_x0, const float* hist_eps,
+                           const float* coef6, int64_t n, float* x_out, float* hist_x0_out, float* hist_eps_out,
+                           void* stream) {
+  if (!x || !v || !hist_x0 || !hist_eps || !coef6 || !x_out || !hist_x0_out || !hist_eps_out) return ADP_ERR_NULL;
+  if (n <= 0) return ADP_ERR_SHAPE;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)v | (uintptr_t)hist_x0 | (uintptr_t)hist_eps | (uintptr_t)x_out |
+                         (uintptr_t)hist_x0_out | (uintptr_t)hist_eps_out;
+  if ((bits & 15) == 0)
+    ADP_LAUNCH(v_step2_kernel<true>, dim3(stream_grid(n)), dim3(256), stream, x, v, hist_x0, hist_eps, coef6, n, x_out,
+               hist_x0_out, hist_eps_out);
+  else
+    ADP_LAUNCH(v_step2_kernel<false>, dim3(stream_grid(n)), dim3(256), stream, x, v, hist_x0, hist_eps, coef6, n, x_out,
+               hist_x0_out, hist_eps_out);
   return ADP_LAUNCH_OK();
 }
 

@@ -1,6 +1,7 @@
 """v-objective diffusion on the gfx950 kernels: `VDiffusion` (training loss) and `VSampler`
 (DDIM-style loop) and `VInpainter` (RePaint-style resampling loop), API-compatible with
 /root/reference/audio_diffusion_pytorch/diffusion.py:15-30, :62-95, :133-190, :300-354.
+`VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own.
 
 Differences from the reference are structural, not numerical:
   * noising (x_noisy, v_target) is one fused kernel (2 reads, 2 writes) instead of ~6 elementwise ops;
@@ -240,6 +241,16 @@ class VSampler(Sampler):
         ab = torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
         return sigmas[:, None].expand(num_steps + 1, b).contiguous(), ab
 
+    def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
+        """Tensors of x's shape that the step update carries from one step to the next (a subclass's history); owned by the
+        sampling run (eager) or by the graph cache entry (replay).  The first-order rotation has none."""
+        return ()
+
+    def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
+        """x_{i+1} from (x_i, v_i) and row i of `_tables`' per-step table; `out` may be x (each element is read, then
+        written).  The one piece a subclass replaces: everything around it in forward / _forward_graph is shared."""
+        return ops.v_step(x, v, row, out=out)
+
     HOIST_MAX_BYTES = 512 << 20  # cap of the hoisted conditioning table (README net: 360 KB per step and batch element)
 
     def _conditioning_table(self, sig: Tensor, num_steps: int, b: int, kwargs) -> Optional[Tensor]:
@@ -274,9 +285,10 @@ class VSampler(Sampler):
             bar = tqdm(range(num_steps), disable=not show_progress)
             host_sigmas = torch.linspace(self.schedule.start, self.schedule.end, num_steps + 1).tolist() \
                 if (show_progress and isinstance(self.schedule, LinearSchedule)) else None
+            bufs = self._step_buffers(x)
             for i in bar:
                 v = self.net(x, sig[i], **kwargs) if cond is None else self.net(x, sig[i], conditioning=cond[i], **kwargs)
-                x = ops.v_step(x, v.contiguous(), ab[i])
+                x = self._step(x, v.contiguous(), ab[i], bufs, None)
                 if host_sigmas is not None:
                     bar.set_description(f"Sampling (noise={host_sigmas[i + 1]:.2f})")
             return x
@@ -307,6 +319,7 @@ class VSampler(Sampler):
             sx, ssig, sab = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(ab[0])
             scond = torch.empty_like(cond[0]) if cond is not None else None  # this step's rows of the hoisted conditioning
             statics = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in live]
+            bufs = self._step_buffers(sx)
             sx.copy_(x)
             ssig.copy_(sig[0])
             sab.copy_(ab[0])
@@ -321,13 +334,13 @@ class VSampler(Sampler):
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # warm-up outside capture
                 v = self.net(sx, ssig, **skw)
-                ops.v_step(sx, v.contiguous(), sab, out=torch.empty_like(sx))
+                self._step(sx, v.contiguous(), sab, bufs, torch.empty_like(sx))
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 v = self.net(sx, ssig, **skw)
-                ops.v_step(sx, v.contiguous(), sab, out=sx)  # in place: each element is read then written
-            entry = (graph, sx, ssig, sab, statics, scond, psig, ctx_tables_under(self.net))
+                self._step(sx, v.contiguous(), sab, bufs, sx)  # in place: each element is read then written
+            entry = (graph, sx, ssig, sab, statics, scond, psig, ctx_tables_under(self.net), bufs)
             self._graph_cache[key] = entry
             self.graph_captures += 1
             while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
@@ -347,6 +360,60 @@ class VSampler(Sampler):
             sab.copy_(ab[i])
             graph.replay()
         return sx.clone()
+
+
+class VMultistepSampler(VSampler):
+    """Second-order two-step (Adams-Bashforth style) exponential integrator for the v-objective: ONE net evaluation per step
+    like `VSampler`, error falling with the square of the step size.  Not in the reference.
+
+    The probability-flow ODE in the angle phi = sigma * pi / 2 is dx/dphi = -sin(phi) x0 + cos(phi) eps.  `VSampler` integrates
+    it with (x0, eps) held constant over a step; this sampler extrapolates both linearly in phi through the previous step's
+    values and integrates that exactly.  With d = phi_{i+1} - phi_i, g = phi_i - phi_{i-1}:
+
+        x_{i+1} = a_{i+1} x0_i + b_{i+1} eps_i + ca_i (x0_i - x0_{i-1}) + cb_i (eps_i - eps_{i-1})
+        ca_i = (d a_{i+1} - b_{i+1} + b_i) / g      cb_i = (d b_{i+1} + a_{i+1} - a_i) / g      ca_0 = cb_0 = 0
+
+    so the first step is the `VSampler` step and one captured graph (U-Net forward + adp_v_step2 in place on x and on the two
+    history buffers of the cache entry) serves every step: steps differ only in their coefficient row, and a row with
+    ca = cb = 0 does not read the history, so nothing of an earlier run can reach the next one.
+    `order=1` is `VSampler`'s arithmetic (A/B in one class)."""
+
+    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), order: int = 2, use_graph: bool = True):
+        if order not in (1, 2):
+            raise ValueError(f"VMultistepSampler: order must be 1 or 2; got {order!r}")
+        super().__init__(net=net, schedule=schedule, use_graph=use_graph)
+        self.order = order
+
+    def _tables(self, num_steps: int, b: int, device):
+        """sigma table [N+1, B] and per-step rows (a_i, b_i, a_{i+1}, b_{i+1}, ca_i, cb_i) [N, 6] on the device.  ca, cb are
+        differences of nearly equal numbers (about d**2 / 2): the table is formed in float64 on the host (one small
+        device-to-host copy per sampling run, none in the loop) and rounded to float32 once."""
+        if self.order == 1:
+            return super()._tables(num_steps, b, device)
+        sigmas = self.schedule(num_steps + 1, device=device).to(torch.float32)  # (what the net is given)
+        phi = sigmas.to(device="cpu", dtype=torch.float64) * (pi / 2)
+        a, bt = torch.cos(phi), torch.sin(phi)
+        d = phi[1:] - phi[:-1]
+        ca, cb = torch.zeros(num_steps, dtype=torch.float64), torch.zeros(num_steps, dtype=torch.float64)
+        if num_steps > 1:
+            g = d[:-1]
+            if bool((g == 0).any()):
+                raise ValueError("VMultistepSampler: the schedule repeats a sigma (zero step before step "
+                                 f"{int((g == 0).nonzero()[0]) + 1}); neighbouring sigmas must differ")
+            ca[1:] = (d[1:] * a[2:] - bt[2:] + bt[1:-1]) / g
+            cb[1:] = (d[1:] * bt[2:] + a[2:] - a[1:-1]) / g
+        coef = torch.stack([a[:-1], bt[:-1], a[1:], bt[1:], ca, cb], dim=1).to(torch.float32).contiguous()
+        return sigmas[:, None].expand(num_steps + 1, b).contiguous(), coef.to(device)
+
+    def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
+        # (x0_{i-1}, eps_{i-1}); left uninitialised: the first step of every run writes them without reading them
+        return () if self.order == 1 else (torch.empty_like(x), torch.empty_like(x))
+
+    def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
+        if self.order == 1:
+            return super()._step(x, v, row, bufs, out)
+        hist_x0, hist_eps = bufs
+        return ops.v_step2(x, v, hist_x0, hist_eps, row, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
 
 
 """ Inpainters """

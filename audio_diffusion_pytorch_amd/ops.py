@@ -606,6 +606,27 @@ def v_step(x: Tensor, v: Tensor, ab4: Tensor, out: Optional[Tensor] = None) -> T
     return out
 
 
+def v_step2(x: Tensor, v: Tensor, hist_x0: Tensor, hist_eps: Tensor, coef6: Tensor, out: Optional[Tensor] = None,
+            hist_x0_out: Optional[Tensor] = None, hist_eps_out: Optional[Tensor] = None):
+    """One second-order multistep sampler update (adp_v_step2): returns (x_next, x0, eps).  Each output may be its input
+    (out=x, hist_x0_out=hist_x0, hist_eps_out=hist_eps); a coef6 row with ca = cb = 0 does not read the history."""
+    n = x.numel()
+    for t in (v, hist_x0, hist_eps, out, hist_x0_out, hist_eps_out):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"v_step2: every tensor must have x's {n} elements; got {t.numel()}")
+    if coef6.numel() != 6:
+        raise ValueError(f"v_step2: coef6 holds (a0, b0, a1, b1, ca, cb); got {coef6.numel()} values")
+    if out is None:
+        out = torch.empty_like(x)
+    if hist_x0_out is None:
+        hist_x0_out = torch.empty_like(x)
+    if hist_eps_out is None:
+        hist_eps_out = torch.empty_like(x)
+    _C.call("adp_v_step2", ptr(x), ptr(v), ptr(hist_x0), ptr(hist_eps), ptr(coef6), n, ptr(out), ptr(hist_x0_out),
+            ptr(hist_eps_out), _C.stream())
+    return out, hist_x0_out, hist_eps_out
+
+
 def v_inpaint_step(x: Tensor, v: Tensor, source: Tensor, noise: Tensor, mask_u8: Tensor, ab4: Tensor,
                    out: Optional[Tensor] = None) -> Tensor:
     if out is None:

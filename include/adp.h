@@ -307,6 +307,12 @@ int adp_mse_fwd(const float* v_pred, const float* v_target, int64_t n, float* lo
 int adp_mse_bwd(const float* v_pred, const float* v_target, const float* gloss, int64_t n, float* dv, void* stream);
 /* one VSampler step: x <- a1*(a0 x - b0 v) + b1*(b0 x + a0 v); ab4 = device [a0, b0, a1, b1] */
 int adp_v_step(const float* x, const float* v, const float* ab4, int64_t n, float* x_out, void* stream);
+/* one VMultistepSampler step (second-order two-step exponential integrator in phi = sigma*pi/2):
+ *   x0 = a0 x - b0 v ; eps = b0 x + a0 v ; x_out = a1 x0 + b1 eps + ca (x0 - hist_x0) + cb (eps - hist_eps) ;
+ *   hist_x0_out = x0 ; hist_eps_out = eps.   coef6 = device [a0, b0, a1, b1, ca, cb].
+ * A row with ca = cb = 0 (the first step of a run) does not read hist_x0 / hist_eps.  Each output may alias its input. */
+int adp_v_step2(const float* x, const float* v, const float* hist_x0, const float* hist_eps, const float* coef6,
+                int64_t n, float* x_out, float* hist_x0_out, float* hist_eps_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-head attention core (a_unet AttentionBase; components.py:92-93): channel-major operands
