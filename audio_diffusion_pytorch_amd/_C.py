@@ -106,6 +106,13 @@ SIGNATURES = {
     "adp_stft_loss_ws_bytes": (I, [I, I, I, P, I]),
     "adp_stft_loss_fwd": (c_int, [P, P, I, I, I, P, F, F, F, F, P, P, P]),
     "adp_stft_loss_bwd": (c_int, [P, P, P, P, I, I, I, P, F, F, F, F, P, P, P]),
+    "adp_mel_frames": (I, [I, I, I]),
+    "adp_mel_spectrogram_ws_bytes": (I, [I, I, I, I, I, I]),
+    "adp_mel_spectrogram": (c_int, [P, P, P, I, I, I, I, I, I, I, I, P, P, P]),
+    "adp_tflat_out_len": (I, [I, I, I]),
+    "adp_tflat_fwd": (c_int, [P, P, I, I, I, I, I, P, P]),
+    "adp_tflat_wgrad_ws_bytes": (I, [I, I, I, I, I]),
+    "adp_tflat_wgrad": (c_int, [P, P, I, I, I, I, I, P, P, P]),
     "adp_ctx_fold_fwd": (c_int, [P, P, P, I, I, I, P, P, P]),
     "adp_ctx_fold_bwd": (c_int, [P, P, P, P, P, I, I, I, P, P, P, P]),
     "adp_attn_fwd": (c_int, [P, P, P, I, I, I, I, I, I, I, P, P, P, P]),

@@ -30,8 +30,10 @@ def _out_of_scope(name: str, why: str):
     return type(name, (), {"__init__": __init__, "__doc__": f"Out of scope: {why}."})
 
 
-DiffusionVocoder = _out_of_scope("DiffusionVocoder", "needs torchaudio's STFT / mel filterbank")
-MelSpectrogram = _out_of_scope("MelSpectrogram", "needs torchaudio's STFT / mel filterbank")
+DiffusionVocoder = _out_of_scope("DiffusionVocoder", "the native vocoder is audio_diffusion_pytorch_amd.vocoder.DiffusionVocoder; "
+                                "this top-level name is still the stub")
+MelSpectrogram = _out_of_scope("MelSpectrogram", "the native mel front end is audio_diffusion_pytorch_amd.vocoder.MelSpectrogram; "
+                              "this top-level name is still the stub")
 DiffusionAR = _out_of_scope("DiffusionAR", "autoregressive ARVDiffusion / ARVSampler use a different net signature")
 
 

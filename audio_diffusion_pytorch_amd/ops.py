@@ -664,6 +664,51 @@ def resample(x: Tensor, kern: Tensor, fi: int, fo: int, width: int, out_len: int
     return out
 
 
+def mel_frames(length: int, n_fft: int, hop: int) -> int:
+    return _C.query("adp_mel_frames", length, n_fft, hop)
+
+
+def mel_spectrogram(x: Tensor, fb: Tensor, mel_range: Optional[Tensor], n_fft: int, hop: int, win: int, normalize: bool,
+                    normalize_log: bool) -> Tensor:
+    """x [rows, T], fb [n_fft // 2 + 1, n_mels], mel_range int32 [n_mels, 2] or None -> [rows, n_mels, frames]
+    (adp_mel_spectrogram)."""
+    rows, T = x.shape
+    n_mels = fb.shape[1]
+    assert fb.shape[0] == n_fft // 2 + 1, "mel_spectrogram: the filterbank is [n_fft // 2 + 1, n_mels]"
+    frames = mel_frames(T, n_fft, hop)
+    out = torch.empty((rows, n_mels, frames), dtype=torch.float32, device=x.device)
+    ws = _ws(_C.query("adp_mel_spectrogram_ws_bytes", rows, T, n_fft, hop, win, n_mels), x) if normalize else None
+    _C.tag(bytes=4 * (x.numel() + out.numel()), shape=f"rows{rows} len{T} fft{n_fft} hop{hop} mel{n_mels}")
+    _C.call("adp_mel_spectrogram", ptr(x), ptr(fb), ptr(mel_range, torch.int32), rows, T, n_fft, hop, win, n_mels,
+            int(bool(normalize)), int(bool(normalize_log)), ptr(out), ptr(ws), _C.stream())
+    return out
+
+
+def tflat_fwd(spec: Tensor, w: Tensor, hop: int) -> Tensor:
+    """spec [N, M, L], w [M, 1, K] -> [N, 1, Lout]: ConvTranspose1d(M, 1, K, stride=hop, padding=(K - hop) // 2) (adp_tflat_fwd)."""
+    N, M, L = spec.shape
+    K = w.shape[2]
+    assert w.shape[0] == M and w.shape[1] == 1, "tflat_fwd: weight is [mel_channels, 1, kernel_size]"
+    out = torch.empty((N, 1, _C.query("adp_tflat_out_len", L, K, hop)), dtype=torch.float32, device=spec.device)
+    _C.tag(flops=2 * out.numel() * M * ((K + hop - 1) // hop), shape=f"N{N} M{M} L{L} K{K} hop{hop}")
+    _C.call("adp_tflat_fwd", ptr(spec), ptr(w), N, M, L, K, hop, ptr(out), _C.stream())
+    return out
+
+
+def tflat_wgrad(spec: Tensor, g: Tensor, K: int, hop: int, dw: Optional[Tensor] = None) -> Tensor:
+    """dW [M, 1, K] of tflat_fwd for the output gradient g [N, 1, Lout]; written, not accumulated (adp_tflat_wgrad)."""
+    N, M, L = spec.shape
+    assert g.shape == (N, 1, _C.query("adp_tflat_out_len", L, K, hop)), "tflat_wgrad: output gradient shape mismatch"
+    if dw is None:
+        dw = torch.empty((M, 1, K), dtype=torch.float32, device=spec.device)
+        if os.environ.get("ADP_DEBUG_POISON", "0") == "1":  # (test-suite: a slice nobody wrote cannot pass)
+            dw.fill_(float("nan"))
+    ws = _ws(_C.query("adp_tflat_wgrad_ws_bytes", N, M, L, K, hop), spec)
+    _C.tag(flops=2 * N * L * M * K, shape=f"N{N} M{M} L{L} K{K} hop{hop}")
+    _C.call("adp_tflat_wgrad", ptr(spec), ptr(g), N, M, L, K, hop, ptr(dw), ptr(ws), _C.stream())
+    return dw
+
+
 def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(a)

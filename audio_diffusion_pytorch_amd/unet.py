@@ -798,7 +798,7 @@ class _Run:
         if has_adapter:
             skip = ops.conv1d(x, blk.skip_adapter.weight, blk.skip_adapter.bias, x2=x2)
         else:
-            assert x2 is None
+            assert x2 is None, "x_append needs the depth-0 skip adapter (in_channels counts the appended channels)"
             skip = x
         wd = blk.down.weight
         self.gn = self.gn_part_for(n.channels[d])  # the first item of every depth is a ResnetItem (GroupNorm of h0)
@@ -859,9 +859,12 @@ class _Run:
                 if has_adapter:
                     ops.conv1d_wgrad(x, gskip, 1, x2=x2, dw=self.g(blk.skip_adapter.weight),
                                      dbias=self.g(blk.skip_adapter.bias))
+                if x2 is not None:
+                    if self.want_x2_grad:  # the appended channels' share of the two data gradients (vocoder: to_flat's output)
+                        self.x2_grad = data_grad(gh, gskip, x.shape[1], wd.shape[1])
+                    return data_grad(gh, gskip, 0, x.shape[1]) if need_dx else None
                 if not need_dx:
                     return None
-                assert x2 is None, "input gradient through an appended-channel input is not needed on the hot path"
                 if has_adapter:
                     gx = ops.conv1d(gskip, blk.skip_adapter.weight, None, transposed=True)
                 else:
@@ -870,6 +873,16 @@ class _Run:
                     return ops.conv1d(gh, wd, None, transposed=True, res=gx)
                 M, R, KT = wd.shape
                 return ops.conv1d(gh, wd.view(M, R * KT, 1), None, transposed=True, store=1, sp=f, res=gx)
+
+            def data_grad(gh, gskip, c0, c1):
+                """Gradient of input channels [c0, c1) of the two-pointer input [x | x2]: skip adapter + down conv, from the
+                matching slices of their weights (the adapter always exists here: x2 widens the input past out_channels)."""
+                gx = ops.conv1d(gskip, blk.skip_adapter.weight[:, c0:c1, :].contiguous(), None, transposed=True)
+                w = wd[:, c0:c1, :].contiguous()
+                if f == 1:
+                    return ops.conv1d(gh, w, None, transposed=True, res=gx)
+                M, R, KT = w.shape
+                return ops.conv1d(gh, w.view(M, R * KT, 1), None, transposed=True, store=1, sp=f, res=gx)
 
             # tape order: [..., bwd_down, items_down..., inner..., items_up..., bwd_up]
             self.tape.insert(tape_mark_down, (bwd_down, d))   # tag d: block d's parameter gradients are complete
@@ -897,6 +910,8 @@ class _UNetFn(torch.autograd.Function):
         run.conditioning(time, features, cond_pre if not need_grad else None)
         run.emb_grad = None
         run.want_emb_grad = bool(embedding is not None and ctx.needs_input_grad[4])
+        run.want_x2_grad = bool(need_grad and x2 is not None and ctx.needs_input_grad[5])
+        run.x2_grad = None
         run.ctx_bank = None
         if embedding is not None and os.environ.get("ADP_CTX_BANK", "1") != "0":
             from .attention import CtxBank
@@ -986,6 +1001,8 @@ class _UNetFn(torch.autograd.Function):
         run.grads.clear()
         run.flat = None
         ctx.run = None
-        out = (None, gx, None, gfeat, gemb, None, None, None, None, None) + gctx + tuple(views)
+        gx2 = run.x2_grad
+        run.x2_grad = None
+        out = (None, gx, None, gfeat, gemb, gx2, None, None, None, None) + gctx + tuple(views)
         del views, flat, v
         return out

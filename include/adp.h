@@ -383,6 +383,41 @@ int adp_stft_loss_bwd(const float* x, const float* y, const float* gloss, const 
                       float* dx, float* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mel spectrogram of `rows` rows of `length` fp32 samples (vocoder.MelSpectrogram; the reference's MelSpectrogram with
+ * torchaudio's documented defaults, center=False):
+ *   reflect padding (n_fft - hop) / 2 on both sides; frames = 1 + (length + 2 pad - n_fft) / hop (adp_mel_frames);
+ *   X = STFT(n_fft, hop, periodic Hann of length win centred in n_fft, onesided, not normalised);
+ *   mel[row, m, t] = sum_k fb[k, m] |X[row, t, k]|, k = 0 .. n_fft/2 in increasing order; fb is DEVICE [n_fft/2 + 1, n_mels];
+ *   range (DEVICE int32 [n_mels, 2], may be NULL) names per mel the bins [lo, hi) outside of which its column of fb is
+ *   zero -- only those are visited; NULL visits every bin;
+ *   normalize: mel = 2 (mel / max over the whole output)^(1/4) - 1, the maximum found on the device (a zero maximum
+ *   gives -1 everywhere);  normalize_log: mel = log(max(mel, 1e-5)), after normalize.
+ * n_fft: power of two in [64, 4096], 1 <= hop <= n_fft, 1 <= win <= n_fft (else ADP_ERR_UNSUPPORTED); length > pad and at
+ * least one frame (else ADP_ERR_SHAPE).  out is [rows, n_mels, frames]; ws (adp_mel_spectrogram_ws_bytes) is needed with
+ * normalize only.  One launch (two with normalize), no atomics, bit-identical from call to call.
+ * ------------------------------------------------------------------------------------------ */
+int64_t adp_mel_frames(int64_t length, int64_t n_fft, int64_t hop);
+int64_t adp_mel_spectrogram_ws_bytes(int64_t rows, int64_t length, int64_t n_fft, int64_t hop, int64_t win, int64_t n_mels);
+int adp_mel_spectrogram(const float* x, const float* fb, const int32_t* range, int64_t rows, int64_t length, int64_t n_fft,
+                        int64_t hop, int64_t win, int64_t n_mels, int64_t normalize, int64_t normalize_log, float* out,
+                        float* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The vocoder's to_flat: ConvTranspose1d(M, 1, kernel_size K, stride hop, padding (K - hop) / 2, bias=False), K >= hop >= 1.
+ *   adp_tflat_out_len: Lout = (L - 1) hop - 2 pad + K.
+ *   adp_tflat_fwd   : out[n, t] = sum_m sum_l spec[n, m, l] w[m, t + pad - l hop]   (spec [N, M, L], w [M, 1, K], out [N, 1, Lout])
+ *   adp_tflat_wgrad : dw[m, k] = sum_n sum_l spec[n, m, l] g[n, l hop + k - pad]    (g [N, 1, Lout]; dw is WRITTEN; the sum runs
+ *                     in segments whose partials go through ws (adp_tflat_wgrad_ws_bytes) and are added in a fixed order).
+ * The spectrogram gets no gradient.  Deterministic; one launch forward, two for the weight gradient.
+ * ------------------------------------------------------------------------------------------ */
+int64_t adp_tflat_out_len(int64_t L, int64_t K, int64_t hop);
+int adp_tflat_fwd(const float* spec, const float* w, int64_t N, int64_t M, int64_t L, int64_t K, int64_t hop, float* out,
+                  void* stream);
+int64_t adp_tflat_wgrad_ws_bytes(int64_t N, int64_t M, int64_t L, int64_t K, int64_t hop);
+int adp_tflat_wgrad(const float* spec, const float* g, int64_t N, int64_t M, int64_t L, int64_t K, int64_t hop, float* dw,
+                    float* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused AdamW step (optim.AdamW: torch.optim.AdamW + clip_grad_norm_(norm_type=2) + an EMA copy of the weights).
  * Both launches walk a DEVICE chunk table of int64 triples [tensor index, first element, count] that the host builds once
  * (fixed-size chunks, so a 1 M-element weight and an 8-element bias balance); blocks stride over it.  Tensors are fp32,
