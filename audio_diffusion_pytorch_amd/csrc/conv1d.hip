@@ -856,6 +856,7 @@ extern "C" int adp_conv1d(const adp_conv_desc* dp, void* stream) {
   if (d.gnb_ab) {  // (the caller asks adp_conv1d_gnb_entries first; a launch that cannot fill gnb_ab must not pretend to)
     if (!d.gnb_x || !d.gnb_stats || !d.gnb_gamma || !d.gnb_beta) return ADP_ERR_NULL;
     if (d.gnb_groups < 1 || d.M % d.gnb_groups != 0) return ADP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(d.gnb_ab) & 7) return ADP_ERR_ALIGN;  // (every family stores its (a, b) pairs as 8 bytes: adp.h)
     if (adp_conv1d_gnb_entries(dp) <= 0) return ADP_ERR_UNSUPPORTED;
   }
   if (adp_conv_tile_eligible(d)) return adp_conv_tile(d, stream);
@@ -905,6 +906,9 @@ extern "C" int64_t adp_conv1d_gnb_entries(const adp_conv_desc* dp) {
   const adp_conv_desc& d = *dp;
   if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0) return ADP_ERR_SHAPE;
   if (d.store != 0) return 0;
+  // every family reads gnb_x with 16-byte loads next to its output tile: an address that does not allow them has no such
+  // epilogue (the caller's GroupNorm backward then runs its own first stage)
+  if (reinterpret_cast<uintptr_t>(d.gnb_x) & 15) return 0;
   if (adp_conv_tile_eligible(d)) return adp_conv_tile_gnb_entries(d);
   if (adp_conv_tilek_eligible(d)) return adp_conv_tilek_gnb_entries(d);
   if (adp_conv_mm4_eligible(d)) return adp_conv_mm4_gnb_entries(d);

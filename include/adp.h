@@ -12,7 +12,10 @@
  *   - plain device pointers (fp32 unless noted), int64 sizes, a hipStream_t passed as void*;
  *   - returns 0 (ADP_OK) or a negative ADP_ERR_* code; never throws, never allocates,
  *     never synchronises: stream-ordered, re-entrant, hipGraph-capturable;
- *   - tensors are contiguous, activations laid out [B, C, L] with L fastest.
+ *   - tensors are contiguous, activations laid out [B, C, L] with L fastest;
+ *   - pointers need only the alignment of their element type unless a function says otherwise: where an address (or
+ *     a length) does not allow the 16- or 8-byte accesses a kernel prefers, the call takes a scalar path or another
+ *     kernel family and returns the same values (up to the summation order); nothing outside the operands is touched.
  */
 #ifndef ADP_H
 #define ADP_H
@@ -91,7 +94,9 @@ typedef struct adp_conv_desc {
      is da.  The epilogue then also leaves the first stage of that backward (what adp_gn_silu_bwd_reduce computes from a pass
      over x and da): gnb_ab[((b*M + m)*E + e)*2 + {0,1}] = (sum ds*xhat, sum ds) over the e-th position slice of row m,
      ds = da * silu'(gamma*xhat + beta), E = adp_conv1d_gnb_entries(d) (0: this launch cannot; leave gnb_ab NULL).
-     The second stage is adp_gn_silu_bwd_apply_ab(..., NSab = E).  components.py:89 (ConvBlock), backward. */
+     The second stage is adp_gn_silu_bwd_apply_ab(..., NSab = E).  components.py:89 (ConvBlock), backward.
+     Alignment: gnb_ab must be 8-byte aligned (ADP_ERR_ALIGN otherwise: the pairs are stored as 8 bytes); a gnb_x that is not
+     16-byte aligned makes adp_conv1d_gnb_entries answer 0 (the epilogue reads it with 16-byte loads). */
   const float* gnb_x;      /* [B, M, N], the GroupNorm's input */
   const float* gnb_stats;  /* [B, gnb_groups, 2] (mean, rstd) */
   const float* gnb_gamma;  /* [M] */
@@ -318,6 +323,8 @@ int adp_v_step2(const float* x, const float* v, const float* hist_x0, const floa
  * Multi-head attention core (a_unet AttentionBase; components.py:92-93): channel-major operands
  *   q [B, H*D, n], k,v [B, H*D, m]  ->  o [B, H*D, n] = softmax(q^T k * D^-0.5) v   per head
  * lse [B, H, n] (log-sum-exp) is written for the backward pass.
+ * q_bstride is the batch stride (floats) of q and dq, kv_bstride that of k, v, dk and dv (q, k | v may be slices of wider
+ * projection outputs); o, dout and lse are packed.
  * ------------------------------------------------------------------------------------------ */
 /* ws: scratch of adp_attn_fwd_ws_bytes() bytes or NULL.  With it, small grids (batch 1) split the key range over
  * several waves per query tile and merge the partial softmax results in a second launch (fixed order). */

@@ -16,13 +16,7 @@ from conftest import rel_err
 TOL = 1e-4  # tighter than the 1e-3 contract on purpose: these are single ops
 
 
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def ref_gn_silu(x, G, gamma, beta):
-    return F.silu(F.group_norm(x, G, gamma, beta, eps=1e-5))
+from refs import gn_silu_as_given as ref_gn_silu, rnd  # noqa: E402  (shared with test_operand_placement.py)
 
 
 # ------------------------------------------------------------------ conv forward family
