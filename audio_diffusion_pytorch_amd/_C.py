@@ -127,11 +127,19 @@ SIGNATURES = {
     "adp_probe_mfma_v": (I, [I, P, I, c_int, P]),
 }
 
+# the extension header include/adp_ar.h (autoregressive v-diffusion), one to one as well; `call` / `query` take names of
+# either table
+AR_SIGNATURES = {
+    "adp_arv_noise": (c_int, [P, P, P, I, I, I, I, P, P, P, P]),
+    "adp_arv_step": (c_int, [P, P, P, I, I, I, I, P, P, P]),
+    "adp_arv_plane": (c_int, [P, I, I, I, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h declares
+    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -34,7 +34,8 @@ DiffusionVocoder = _out_of_scope("DiffusionVocoder", "the native vocoder is audi
                                 "this top-level name is still the stub")
 MelSpectrogram = _out_of_scope("MelSpectrogram", "the native mel front end is audio_diffusion_pytorch_amd.vocoder.MelSpectrogram; "
                               "this top-level name is still the stub")
-DiffusionAR = _out_of_scope("DiffusionAR", "autoregressive ARVDiffusion / ARVSampler use a different net signature")
+DiffusionAR = _out_of_scope("DiffusionAR", "the native autoregressive path (DiffusionAR, ARVDiffusion, ARVSampler) is "
+                           "audio_diffusion_pytorch_amd.ar; this top-level name is still the stub")
 
 
 def LTPlugin(*args, **kwargs):

@@ -1,4 +1,4 @@
-"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of include/adp.h) in-tree with hipcc.
+"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of include/adp.h and include/adp_ar.h) in-tree with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the resulting
 .so travels to the GPU box with the repository snapshot.  No CUDA path, no hipify, no fallback.
@@ -24,7 +24,8 @@ def sources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     srcs = sources()
-    deps = srcs + [os.path.join(CSRC, "adp_rt.h"), os.path.join(CSRC, "conv_internal.h"), os.path.join(CSRC, "conv_mm_impl.h"), os.path.join(REPO_ROOT, "include", "adp.h")]
+    deps = srcs + [os.path.join(CSRC, "adp_rt.h"), os.path.join(CSRC, "conv_internal.h"), os.path.join(CSRC, "conv_mm_impl.h"), os.path.join(REPO_ROOT, "include", "adp.h"),
+                   os.path.join(REPO_ROOT, "include", "adp_ar.h")]
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= _newest_mtime(deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

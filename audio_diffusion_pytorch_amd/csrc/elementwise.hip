@@ -3,12 +3,14 @@
 //   adp_mse_*    : diffusion.py:95      F.mse_loss(v_pred, v_target) and its gradient
 //   adp_v_step   : diffusion.py:185-187 one VSampler update, 2 reads 1 write
 //   adp_v_step2  : one VMultistepSampler update (two-step exponential integrator), 4 reads 3 writes
+//   adp_arv_*    : diffusion.py:118-127, :231-235  autoregressive v-diffusion: one noise level per split of the window
 //   adp_time_fourier_* : a_unet NumberEmbedder under TimeConditioningPlugin (components.py:74-76)
 #include "adp_rt.h"
 #ifndef ADP_EMULATE
 #include <mutex>
 #endif
 #include "adp.h"
+#include "adp_ar.h"
 
 namespace {
 
@@ -468,6 +470,127 @@ __global__ __launch_bounds__(256) void adamw_step_kernel(const adp_adamw_tensor*
   }
 }
 
+// ---- autoregressive v-diffusion (ARVDiffusion / ARVSampler): the window of T positions is cut into N splits of l = T / N
+// positions and every split has its own noise level, which the net also reads as an extra input channel (the "sigma plane",
+// [B, T]).  Work item = one (batch or batch-free, split, chunk of the split): blockIdx.x = (bs * gx + chunk).  A thread owns
+// positions of ONE split and walks the channels (and, where the coefficients do not depend on the batch, the batch rows), so
+// the per-split values are formed once per thread, not once per element.  VEC: l % 4 == 0 and every pointer is 16-byte
+// aligned, so every (row, split) segment starts on a 16-byte boundary; else the scalar path.  Each element is read, then
+// written, by the lane that owns it: x_out may be x.
+template <bool VEC>
+__global__ __launch_bounds__(256) void arv_noise_kernel(const float* x, const float* noise, const float* sigma, int64_t C,
+                                                        int64_t T, int64_t N, int64_t gx, float* x_noisy, float* v_target,
+                                                        float* plane) {
+  const int64_t bs = blockIdx.x / gx, chunk = blockIdx.x - bs * gx;
+  const int64_t b = bs / N, s = bs - b * N, l = T / N;
+  const float sg = sigma[bs];
+  // angle = sigma * pi / 2 evaluated left to right in fp32, as v_noise_kernel does
+  const float angle = (sg * PI_F) / 2.0f;
+  const float a = cosf(angle), bt = sinf(angle);
+  const int64_t tid = chunk * 256 + threadIdx.x, nthreads = gx * 256;
+  const int64_t seg = b * C * T + s * l;  // first element of channel 0's segment
+  if (VEC) {
+    for (int64_t j = 4 * tid; j < l; j += 4 * nthreads) {
+      for (int64_t c = 0; c < C; ++c) {
+        const int64_t i = seg + c * T + j;
+        const f32x4 xv = *(const f32x4*)(x + i), nv = *(const f32x4*)(noise + i);
+        f32x4 xn, vt;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          xn[k] = a * xv[k] + bt * nv[k];
+          vt[k] = a * nv[k] - bt * xv[k];
+        }
+        *(f32x4*)(x_noisy + i) = xn;
+        *(f32x4*)(v_target + i) = vt;
+      }
+      const f32x4 sv = {sg, sg, sg, sg};
+      *(f32x4*)(plane + b * T + s * l + j) = sv;
+    }
+  } else {
+    for (int64_t j = tid; j < l; j += nthreads) {
+      for (int64_t c = 0; c < C; ++c) {
+        const int64_t i = seg + c * T + j;
+        const float xv = x[i], nv = noise[i];
+        x_noisy[i] = a * xv + bt * nv;
+        v_target[i] = a * nv - bt * xv;
+      }
+      plane[b * T + s * l + j] = sg;
+    }
+  }
+}
+
+struct ArvCoef {
+  float a0, b0, a1, b1, sigma1;
+};
+
+__device__ __forceinline__ float arv_step_elem(const ArvCoef& c, float xv, float vv) {
+  const float x_pred = c.a0 * xv - c.b0 * vv;  // (the operation order of v_step_kernel)
+  const float n_pred = c.b0 * xv + c.a0 * vv;
+  return c.a1 * x_pred + c.b1 * n_pred;
+}
+
+// blockIdx.x = s * gx + chunk: the coefficients are the split's, the same for every batch row and channel (rows = B * C)
+template <bool VEC>
+__global__ __launch_bounds__(256) void arv_step_kernel(const float* x, const float* v, const float* coef, int64_t B,
+                                                       int64_t C, int64_t T, int64_t N, int64_t gx, float* xo,
+                                                       float* plane) {
+  const int64_t s = blockIdx.x / gx, chunk = blockIdx.x - s * gx;
+  const int64_t l = T / N, rows = B * C;
+  const float* row = coef + 5 * s;
+  const ArvCoef c{row[0], row[1], row[2], row[3], row[4]};
+  const int64_t tid = chunk * 256 + threadIdx.x, nthreads = gx * 256;
+  if (VEC) {
+    for (int64_t j = 4 * tid; j < l; j += 4 * nthreads) {
+      for (int64_t r = 0; r < rows; ++r) {
+        const int64_t i = r * T + s * l + j;
+        const f32x4 xv = *(const f32x4*)(x + i), vv = *(const f32x4*)(v + i);
+        f32x4 xn;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xn[k] = arv_step_elem(c, xv[k], vv[k]);
+        *(f32x4*)(xo + i) = xn;
+      }
+      if (plane) {
+        const f32x4 sv = {c.sigma1, c.sigma1, c.sigma1, c.sigma1};
+        for (int64_t b = 0; b < B; ++b) *(f32x4*)(plane + b * T + s * l + j) = sv;
+      }
+    }
+  } else {
+    for (int64_t j = tid; j < l; j += nthreads) {
+      for (int64_t r = 0; r < rows; ++r) {
+        const int64_t i = r * T + s * l + j;
+        xo[i] = arv_step_elem(c, x[i], v[i]);
+      }
+      if (plane)
+        for (int64_t b = 0; b < B; ++b) plane[b * T + s * l + j] = c.sigma1;
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void arv_plane_kernel(const float* sigma, int64_t B, int64_t T, int64_t N, int64_t gx,
+                                                        float* plane) {
+  const int64_t s = blockIdx.x / gx, chunk = blockIdx.x - s * gx;
+  const int64_t l = T / N;
+  const float sg = sigma[s];
+  const int64_t tid = chunk * 256 + threadIdx.x, nthreads = gx * 256;
+  if (VEC) {
+    const f32x4 sv = {sg, sg, sg, sg};
+    for (int64_t j = 4 * tid; j < l; j += 4 * nthreads)
+      for (int64_t b = 0; b < B; ++b) *(f32x4*)(plane + b * T + s * l + j) = sv;
+  } else {
+    for (int64_t j = tid; j < l; j += nthreads)
+      for (int64_t b = 0; b < B; ++b) plane[b * T + s * l + j] = sg;
+  }
+}
+
+// blocks per split: four positions per thread and pass; `units` splits (or batch x split pairs) share the launch
+int64_t arv_grid(int64_t l, int64_t units) {
+  int64_t gx = adp_cdiv(l, 256 * 4);
+  const int64_t cap = adp_cdiv(4096, units);  // about the block count stream_grid allows
+  if (gx > cap) gx = cap;
+  return gx < 1 ? 1 : gx;
+}
+
 unsigned stream_grid(int64_t n) {
   int64_t g = adp_cdiv(n, 256 * 4);
   if (g > 4096) g = 4096;
@@ -618,6 +741,50 @@ extern "C" int adp_v_step2(const float* x, const float* v, const float* hist_x0,
   else
     ADP_LAUNCH(v_step2_kernel<false>, dim3(stream_grid(n)), dim3(256), stream, x, v, hist_x0, hist_eps, coef6, n, x_out,
                hist_x0_out, hist_eps_out);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_arv_noise(const float* x, const float* noise, const float* sigma, int64_t B, int64_t C, int64_t T,
+                             int64_t N, float* x_noisy, float* v_target, float* sigma_plane, void* stream) {
+  if (!x || !noise || !sigma || !x_noisy || !v_target || !sigma_plane) return ADP_ERR_NULL;
+  if (B <= 0 || C <= 0 || T <= 0 || N <= 0 || T % N != 0) return ADP_ERR_SHAPE;
+  const int64_t l = T / N, gx = arv_grid(l, B * N);
+  if (B * N * gx > 0x7fffffff) return ADP_ERR_SHAPE;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)noise | (uintptr_t)x_noisy | (uintptr_t)v_target | (uintptr_t)sigma_plane;
+  if ((bits & 15) == 0 && l % 4 == 0)
+    ADP_LAUNCH(arv_noise_kernel<true>, dim3((unsigned)(B * N * gx)), dim3(256), stream, x, noise, sigma, C, T, N, gx,
+               x_noisy, v_target, sigma_plane);
+  else
+    ADP_LAUNCH(arv_noise_kernel<false>, dim3((unsigned)(B * N * gx)), dim3(256), stream, x, noise, sigma, C, T, N, gx,
+               x_noisy, v_target, sigma_plane);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_arv_step(const float* x, const float* v, const float* coef, int64_t B, int64_t C, int64_t T, int64_t N,
+                            float* x_out, float* sigma_plane_out, void* stream) {
+  if (!x || !v || !coef || !x_out) return ADP_ERR_NULL;
+  if (B <= 0 || C <= 0 || T <= 0 || N <= 0 || T % N != 0) return ADP_ERR_SHAPE;
+  const int64_t l = T / N, gx = arv_grid(l, N);
+  if (N * gx > 0x7fffffff) return ADP_ERR_SHAPE;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)v | (uintptr_t)x_out | (uintptr_t)sigma_plane_out;
+  if ((bits & 15) == 0 && l % 4 == 0)
+    ADP_LAUNCH(arv_step_kernel<true>, dim3((unsigned)(N * gx)), dim3(256), stream, x, v, coef, B, C, T, N, gx, x_out,
+               sigma_plane_out);
+  else
+    ADP_LAUNCH(arv_step_kernel<false>, dim3((unsigned)(N * gx)), dim3(256), stream, x, v, coef, B, C, T, N, gx, x_out,
+               sigma_plane_out);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_arv_plane(const float* sigma, int64_t B, int64_t T, int64_t N, float* sigma_plane, void* stream) {
+  if (!sigma || !sigma_plane) return ADP_ERR_NULL;
+  if (B <= 0 || T <= 0 || N <= 0 || T % N != 0) return ADP_ERR_SHAPE;
+  const int64_t l = T / N, gx = arv_grid(l, N);
+  if (N * gx > 0x7fffffff) return ADP_ERR_SHAPE;
+  if (((uintptr_t)sigma_plane & 15) == 0 && l % 4 == 0)
+    ADP_LAUNCH(arv_plane_kernel<true>, dim3((unsigned)(N * gx)), dim3(256), stream, sigma, B, T, N, gx, sigma_plane);
+  else
+    ADP_LAUNCH(arv_plane_kernel<false>, dim3((unsigned)(N * gx)), dim3(256), stream, sigma, B, T, N, gx, sigma_plane);
   return ADP_LAUNCH_OK();
 }
 

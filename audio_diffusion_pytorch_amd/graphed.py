@@ -13,6 +13,7 @@ sequence (one autograd node for the whole U-Net, no host reads), so `VDiffusion.
 the autograd node `_Replay` hands the flat buffer's per-parameter views to autograd, so AccumulateGrad, parameter hooks,
 gradient accumulation, `loss / k` scaling (the incoming gradient is a static input of graph B) and optimizers behave as in the
 eager step.  What is captured is exactly the eager path (`VDiffusion._forward_eager`), kernels and arithmetic unchanged.
+`ar.ARVDiffusion` replays its step through the same cache (it provides `loss_fn`, `sigma_distribution` and `_forward_eager`).
 
 Taken only where it is safe, else the eager step runs as before (never an error): CUDA tensors, grad mode on, the stock
 `UniformDistribution`, inputs / conditioning tensors that do not require grad, keyword arguments that can be made static

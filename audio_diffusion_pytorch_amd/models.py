@@ -12,7 +12,7 @@ What is organised around the gfx950 kernels rather than around torch ops:
     never writes its input, so no defensive clone;
   * the appended / injected conditioning tensors are consumed through a second input pointer of the depth-0 /
     inject convs (components.AppendChannelsPlugin, unet inject items): no concatenated copy exists.
-Vocoder / AR wrappers are outside the hot-path scope.
+The vocoder and the autoregressive wrapper live in vocoder.py and ar.py.
 """
 from abc import ABC, abstractmethod
 from typing import Any, Callable, Dict, Optional, Sequence, Tuple, Union

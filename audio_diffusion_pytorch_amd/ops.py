@@ -627,6 +627,64 @@ def v_step2(x: Tensor, v: Tensor, hist_x0: Tensor, hist_eps: Tensor, coef6: Tens
     return out, hist_x0_out, hist_eps_out
 
 
+def _arv_dims(what: str, x: Tensor, N: int):
+    if x.dim() != 3:
+        raise ValueError(f"{what}: x must be [B, C, T]; got {tuple(x.shape)}")
+    B, C, T = x.shape
+    if N < 1 or T % N != 0:
+        raise ValueError(f"{what}: the length {T} must be divisible by num_splits={N}")
+    return B, C, T
+
+
+def arv_noise(x: Tensor, noise: Tensor, sigma: Tensor):
+    """ARVDiffusion's noising (adp_arv_noise): x, noise [B, C, T], sigma [B, N] (one level per batch row and split) ->
+    (x_noisy, v_target, sigma_plane [B, 1, T])."""
+    if sigma.dim() != 2 or sigma.shape[0] != x.shape[0]:
+        raise ValueError(f"arv_noise: sigma must be [B, num_splits]; got {tuple(sigma.shape)} for x {tuple(x.shape)}")
+    N = sigma.shape[1]
+    B, C, T = _arv_dims("arv_noise", x, N)
+    if noise.shape != x.shape:
+        raise ValueError(f"arv_noise: noise must have x's shape {tuple(x.shape)}; got {tuple(noise.shape)}")
+    x_noisy, v_target = torch.empty_like(x), torch.empty_like(x)
+    plane = torch.empty((B, 1, T), dtype=torch.float32, device=x.device)
+    _C.call("adp_arv_noise", ptr(x), ptr(noise), ptr(sigma), B, C, T, N, ptr(x_noisy), ptr(v_target), ptr(plane),
+            _C.stream())
+    return x_noisy, v_target, plane
+
+
+def arv_step(x: Tensor, v: Tensor, coef: Tensor, out: Optional[Tensor] = None, plane_out: Optional[Tensor] = None) -> Tensor:
+    """One ARVSampler update (adp_arv_step): coef [N, 5] holds (a_i, b_i, a_{i+1}, b_{i+1}, sigma_{i+1}) per split.  `out`
+    may be x; `plane_out` ([B, 1, T] or [B, T]), when given, receives the next step's sigma plane."""
+    if coef.dim() != 2 or coef.shape[1] != 5:
+        raise ValueError(f"arv_step: coef must be [num_splits, 5]; got {tuple(coef.shape)}")
+    N = coef.shape[0]
+    B, C, T = _arv_dims("arv_step", x, N)
+    for t in (v, out):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"arv_step: v and out must have x's shape {tuple(x.shape)}; got {tuple(t.shape)}")
+    if plane_out is not None and plane_out.numel() != B * T:
+        raise ValueError(f"arv_step: plane_out must hold B * T = {B * T} values; got {plane_out.numel()}")
+    if out is None:
+        out = torch.empty_like(x)
+    _C.call("adp_arv_step", ptr(x), ptr(v), ptr(coef), B, C, T, N, ptr(out), ptr(plane_out), _C.stream())
+    return out
+
+
+def arv_plane(sigma: Tensor, B: int, T: int, out: Optional[Tensor] = None) -> Tensor:
+    """sigma [N] -> sigma plane [B, 1, T] with plane[b, 0, t] = sigma[t // (T // N)] (adp_arv_plane)."""
+    if sigma.dim() != 1:
+        raise ValueError(f"arv_plane: sigma must be [num_splits]; got {tuple(sigma.shape)}")
+    N = sigma.shape[0]
+    if B < 1 or T < 1 or N < 1 or T % N != 0:
+        raise ValueError(f"arv_plane: B={B} and T={T} must be positive and T divisible by num_splits={N}")
+    if out is None:
+        out = torch.empty((B, 1, T), dtype=torch.float32, device=sigma.device)
+    elif out.numel() != B * T:
+        raise ValueError(f"arv_plane: out must hold B * T = {B * T} values; got {out.numel()}")
+    _C.call("adp_arv_plane", ptr(sigma), B, T, N, ptr(out), _C.stream())
+    return out
+
+
 def v_inpaint_step(x: Tensor, v: Tensor, source: Tensor, noise: Tensor, mask_u8: Tensor, ab4: Tensor,
                    out: Optional[Tensor] = None) -> Tensor:
     if out is None:
