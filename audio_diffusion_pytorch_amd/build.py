@@ -3,6 +3,7 @@
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the resulting
 .so travels to the GPU box with the repository snapshot.  No CUDA path, no hipify, no fallback.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -22,10 +23,14 @@ def sources():
     return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
 
+def headers():
+    """Every header a kernel source may include (csrc/ and include/): a new one cannot be forgotten."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(REPO_ROOT, "include", "*.h")))
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     srcs = sources()
-    deps = srcs + [os.path.join(CSRC, "adp_rt.h"), os.path.join(CSRC, "conv_internal.h"), os.path.join(CSRC, "conv_mm_impl.h"), os.path.join(REPO_ROOT, "include", "adp.h"),
-                   os.path.join(REPO_ROOT, "include", "adp_ar.h")]
+    deps = srcs + headers()
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= _newest_mtime(deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

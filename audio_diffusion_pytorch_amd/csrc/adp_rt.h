@@ -2,6 +2,7 @@
 // The product build is plain HIP.  -DADP_EMULATE (tests only, see tests/emul/) swaps in a
 // host-side SIMT emulator header that is NOT part of this package.
 #pragma once
+#include <stdlib.h>
 
 #define ADP_OK 0
 #define ADP_ERR_SHAPE (-1)
@@ -241,3 +242,14 @@ __device__ __forceinline__ float adp_dgelu(float x) {
   return cdf + x * pdf;
 }
 static inline int64_t adp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// A/B and test knobs from the environment.  Every call reads the environment again: the tests flip knobs inside one process.
+static inline const char* adp_knob_raw(const char* name) { return getenv(name); }  // the text itself (nullptr: unset), for the few knobs with a rule of their own
+static inline int64_t adp_knob(const char* name, int64_t dflt) {  // integer knob with a default
+  const char* e = adp_knob_raw(name);
+  return e ? atoll(e) : dflt;
+}
+static inline bool adp_knob_on(const char* name, bool dflt = true) {  // switch: off when set and starting with '0', on when set otherwise
+  const char* e = adp_knob_raw(name);
+  return e ? e[0] != '0' : dflt;
+}

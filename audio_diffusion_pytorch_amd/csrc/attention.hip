@@ -965,8 +965,7 @@ extern "C" int adp_attn_fwd(const float* q, const float* k, const float* v, int6
   const int64_t ns = ws ? q_nsplit(B, H, n, m, &tps) : 1;
   if (ns == 1) tps = adp_cdiv(m, 32);
   {  // few keys (cross attention over the embedding): four waves per query tile (ADP_ATTN_FEWKEYS=0: the one-wave form, A/B)
-    const char* fk = getenv("ADP_ATTN_FEWKEYS");
-    if (D == 64 && m <= 64 && ns == 1 && (!fk || fk[0] != '0')) {
+    if (D == 64 && m <= 64 && ns == 1 && adp_knob_on("ADP_ATTN_FEWKEYS")) {
       ADP_LAUNCH(attn_fwd_fewkeys_kernel, dim3((unsigned)adp_cdiv(n, 32), (unsigned)H, (unsigned)B), dim3(256), stream, q, k, v,
                  (int)H, (int)n, (int)m, q_bstride, kv_bstride, scale, o, lse);
       return ADP_LAUNCH_OK();
@@ -1027,13 +1026,11 @@ extern "C" int adp_attn_bwd(const float* q, const float* k, const float* v, cons
     qstride = B * q_bstride;
   }
   {  // few keys: four waves per query tile / per query slice in one launch (ADP_ATTN_FEWKEYS=0: the one-wave forms, A/B)
-    const char* fk = getenv("ADP_ATTN_FEWKEYS");
     // (taken while the query tiles are few: at 1024+ the chip is full of one-wave items either way -- hipGraph microbench, us per
     // backward, one-wave forms -> this kernel: batch 1 n = 128 16.4 -> 9.8, 256 16.2 -> 9.5, 1024 20.9 -> 17.0, 4096 52.1 ->
     // 51.3; batch 4 n = 256 20.0 -> 15.9, n = 1024 40.4 -> 45.6, n = 4096 123 -> 177)
-    if (D == 64 && m <= 64 && B * H * qtiles <= (B * H <= 8 ? 1024 : 512) && (!fk || fk[0] != '0')) {
-      const char* et = getenv("ADP_ATTN_FK_SLICES");
-      int64_t ns4 = (et ? atoi(et) : 512) / (B * H);  // ~two workgroups per CU for the key-major role
+    if (D == 64 && m <= 64 && B * H * qtiles <= (B * H <= 8 ? 1024 : 512) && adp_knob_on("ADP_ATTN_FEWKEYS")) {
+      int64_t ns4 = adp_knob("ADP_ATTN_FK_SLICES", 512) / (B * H);  // ~two workgroups per CU for the key-major role
       if (ns4 > qtiles) ns4 = qtiles;
       if (ns4 > 32) ns4 = 32;
       if (ns4 < 1) ns4 = 1;
@@ -1048,7 +1045,7 @@ extern "C" int adp_attn_bwd(const float* q, const float* k, const float* v, cons
       a.ns = (int)ns4, a.tps = (int)tps4, a.pstride = pstride, a.gq = (int)qtiles;
       unsigned gx4 = (unsigned)(qtiles + ns4);
 #ifdef ADP_ATTN_FK_DEBUG
-      if (const char* eo = getenv("ADP_ATTN_FK_ONLY")) {  // timing only (results incomplete): one role alone
+      if (const char* eo = adp_knob_raw("ADP_ATTN_FK_ONLY")) {  // timing only (results incomplete): one role alone
         if (eo[0] == 'q') gx4 = (unsigned)qtiles;
         if (eo[0] == 'k') a.gq = 0, gx4 = (unsigned)ns4;
       }
@@ -1069,8 +1066,7 @@ extern "C" int adp_attn_bwd(const float* q, const float* k, const float* v, cons
   // separate -> merged: cross attention over 64 keys n = 128 27.6 -> 16.6, n = 1024 32.3 -> 20.7, n = 4096 (1536 waves) 52.3 ->
   // 53.1; self attention n = 256 35.1 -> 21.7, n = 1024 (2048 waves: the chip is full either way and the key-major pass pays
   // for its O columns) 107 -> 127).  ADP_ATTN_MERGE=0 / 1 forces either form (tests, A/B).
-  const char* em = getenv("ADP_ATTN_MERGE");
-  const bool merge = em ? em[0] != '0' : (int64_t)(gq2.x + gkv.x) * H * B * 4 <= 1024;
+  const bool merge = adp_knob_on("ADP_ATTN_MERGE", (int64_t)(gq2.x + gkv.x) * H * B * 4 <= 1024);
   if (merge) {
     attn_bwd_args a;
     a.q = q, a.k = k, a.v = v, a.o = o, a.dout = dout, a.lse = lse;

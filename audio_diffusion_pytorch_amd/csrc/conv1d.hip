@@ -742,8 +742,8 @@ int launch_conv_s1(const adp_conv_desc& d, void* stream) {
   return ADP_LAUNCH_OK();
 }
 
-// tile choice (shared with adp_conv1d_tile): 32-row tiles for narrow layers, 128x128 when that still fills
-// the chip with >= 1.5 workgroups per CU, else 64x64
+// the generic kernels' tile: 32-row tiles for narrow layers, 128x128 when that still fills the chip with >= 1.5 workgroups
+// per CU, else 64x64 (BM * 1000 + BN)
 int64_t pick_tile(const adp_conv_desc& d) {
   if (d.M <= 32) return 32 * 1000 + 128;
   if (d.stride != 4) {
@@ -773,7 +773,30 @@ int dispatch_conv(const adp_conv_desc& d, void* stream) {
   return launch_conv<64, 64, 32, 32, KT, S>(d, stream);
 }
 
-void wgrad_split(const adp_wgrad_desc& d, int BKN, int64_t* PS, int64_t* SPB) {
+int launch_generic(const adp_conv_desc& d, void* stream) {
+  if (d.KT == 1) return dispatch_conv<1, 1>(d, stream);
+  if (d.KT == 2) return dispatch_conv<2, 2>(d, stream);
+  if (d.KT == 3) return dispatch_conv<3, 1>(d, stream);
+  return dispatch_conv<4, 4>(d, stream);
+}
+
+// first row of a family table that accepts the descriptor (the last row of either table, this file's kernels, accepts everything)
+template <class F, class D> const F& first_eligible(const F* const* f, const D& d) {
+  while (!(*f)->eligible(d)) ++f;
+  return **f;
+}
+
+// THE dispatch order of adp_conv1d: its launch and all four queries serve a descriptor from the first eligible row
+const adp_conv_family& conv_family(const adp_conv_desc& d) {
+  static const adp_conv_family generic = {"generic", [](const adp_conv_desc&) { return true; }, launch_generic,
+                                          nullptr, nullptr, nullptr, pick_tile};
+  static const adp_conv_family* const conv_families[] = {&adp_family_tile(), &adp_family_tilek(), &adp_family_mm4(), &adp_family_tilek1(),
+                                                         &adp_family_mm(), &adp_family_direct(), &generic};
+  return first_eligible(conv_families, d);
+}
+
+// positions per split, splits per batch element; returns the number of splits (= partial sums in d.ws)
+int64_t wgrad_split(const adp_wgrad_desc& d, int BKN, int64_t* PS, int64_t* SPB) {
   const int64_t tiles = adp_cdiv(d.M, 32) * adp_cdiv(d.R, 32);
   int64_t want = adp_cdiv(1024, tiles);                       // target ~1024 workgroups
   int64_t spb = adp_cdiv(want, d.B);
@@ -783,17 +806,16 @@ void wgrad_split(const adp_wgrad_desc& d, int BKN, int64_t* PS, int64_t* SPB) {
   int64_t ps = adp_cdiv(adp_cdiv(d.N, spb), BKN) * BKN;
   *PS = ps;
   *SPB = adp_cdiv(d.N, ps);
+  return d.B * *SPB;
 }
-
-int wgrad_bkn(int64_t S) { return S == 4 ? 64 : 128; }
 
 // wide stride-1 layers take the pipelined 64x64 kernel
 bool wgrad_s1_eligible(const adp_wgrad_desc& d) {
   return d.stride == 1 && (d.KT == 1 || d.KT == 3) && (d.up == 1 || d.up == 2 || d.up == 4) && d.prologue != 2 &&
          (d.M > 32 || d.R > 32);
 }
-// chunks per batch element, chunks per split, number of splits (~2 workgroups per CU)
-void wgrad_s1_split(const adp_wgrad_desc& d, int64_t* CPB, int64_t* CPS, int64_t* nsplit) {
+// chunks per batch element, chunks per split; returns the number of splits (~2 workgroups per CU)
+int64_t wgrad_s1_split(const adp_wgrad_desc& d, int64_t* CPB, int64_t* CPS) {
   const int64_t tiles = adp_cdiv(d.M, 64) * adp_cdiv(d.R, 64);
   const int64_t cpb = adp_cdiv(d.N, 64), total = d.B * cpb;
   int64_t ns = adp_cdiv(512, tiles);
@@ -802,53 +824,91 @@ void wgrad_s1_split(const adp_wgrad_desc& d, int64_t* CPB, int64_t* CPS, int64_t
   const int64_t cps = adp_cdiv(total, ns);
   *CPB = cpb;
   *CPS = cps;
-  *nsplit = adp_cdiv(total, cps);
+  return adp_cdiv(total, cps);
 }
 
 template <int KT>
 int launch_wgrad_s1(const adp_wgrad_desc& d, void* stream) {
-  int64_t CPB, CPS, nsplit;
-  wgrad_s1_split(d, &CPB, &CPS, &nsplit);
+  int64_t CPB, CPS;
+  const int64_t nsplit = wgrad_s1_split(d, &CPB, &CPS);
   dim3 grid((unsigned)nsplit, (unsigned)adp_cdiv(d.M, 64), (unsigned)adp_cdiv(d.R, 64));
   ADP_LAUNCH((wgrad_s1_kernel<KT>), grid, dim3(256), stream, d, CPS, CPB, nsplit);
-  if (nsplit > 1) {
-    return adp_wgrad_reduce(d.ws, nsplit, d.M * d.R * KT, d.M, d.dw, d.dbias, (int)(d.accumulate & 1), stream);
-  }
-  return ADP_LAUNCH_OK();
+  if (nsplit == 1) return ADP_LAUNCH_OK();
+  return adp_wgrad_reduce(d.ws, nsplit, d.M * d.R * KT, d.M, d.dw, d.dbias, (int)(d.accumulate & 1), stream);
 }
 
 template <int KT, int S>
 int launch_wgrad(const adp_wgrad_desc& d, void* stream) {
-  if constexpr (S == 1) {
-    if (wgrad_s1_eligible(d)) return launch_wgrad_s1<KT>(d, stream);
-  }
   int64_t PS, SPB;
-  wgrad_split(d, WgradCfg<KT, S>::BKN, &PS, &SPB);
-  const int64_t nsplit = d.B * SPB;
+  const int64_t nsplit = wgrad_split(d, WgradCfg<KT, S>::BKN, &PS, &SPB);
   dim3 grid((unsigned)nsplit, (unsigned)adp_cdiv(d.M, 32), (unsigned)adp_cdiv(d.R, 32));
   ADP_LAUNCH((wgrad_kernel<KT, S>), grid, dim3(256), stream, d, PS, SPB);
   return adp_wgrad_reduce(d.ws, nsplit, d.M * d.R * KT, d.M, d.dw, d.dbias, (int)(d.accumulate & 1), stream);
+}
+
+int64_t wgrad_s1_ws_floats(const adp_wgrad_desc& d) {
+  int64_t CPB, CPS;
+  return wgrad_s1_split(d, &CPB, &CPS) * (d.M * d.R * d.KT + d.M);
+}
+int64_t wgrad_generic_ws_floats(const adp_wgrad_desc& d) {
+  int64_t PS, SPB;
+  return wgrad_split(d, d.stride == 4 ? 64 : 128, &PS, &SPB) * (d.M * d.R * d.KT + d.M);  // (WgradCfg::BKN)
+}
+
+int launch_wgrad_generic(const adp_wgrad_desc& d, void* stream) {
+  if (d.KT == 1) return launch_wgrad<1, 1>(d, stream);
+  if (d.KT == 2) return launch_wgrad<2, 2>(d, stream);
+  if (d.KT == 3) return launch_wgrad<3, 1>(d, stream);
+  return launch_wgrad<4, 4>(d, stream);
+}
+
+// THE dispatch order of adp_conv1d_wgrad, its two queries and adp_conv1d_wgrad_batch
+const adp_wgrad_family& wgrad_family(const adp_wgrad_desc& d) {
+  static const adp_wgrad_family s1 = {
+      "wgrad_s1", wgrad_s1_eligible,
+      [](const adp_wgrad_desc& d, void* stream) { return d.KT == 1 ? launch_wgrad_s1<1>(d, stream) : launch_wgrad_s1<3>(d, stream); },
+      wgrad_s1_ws_floats, nullptr, nullptr};
+  static const adp_wgrad_family generic = {"wgrad_generic", [](const adp_wgrad_desc&) { return true; }, launch_wgrad_generic,
+                                           wgrad_generic_ws_floats, nullptr, nullptr};
+  static const adp_wgrad_family* const wgrad_families[] = {&adp_wgrad_family_mm(), &adp_wgrad_family_direct(), &s1, &generic};
+  return first_eligible(wgrad_families, d);
 }
 
 bool ks_supported(int64_t KT, int64_t S) {
   return (KT == 1 && S == 1) || (KT == 2 && S == 2) || (KT == 3 && S == 1) || (KT == 4 && S == 4);
 }
 
-}  // namespace
+// all a query function checks of a descriptor of either type
+template <class D> bool dims_ok(const D& d) { return d.B > 0 && d.R > 0 && d.M > 0 && d.N > 0 && d.Lin > 0; }
 
-extern "C" int64_t adp_conv1d_gnb_entries(const adp_conv_desc* dp);
-
-extern "C" int adp_conv1d(const adp_conv_desc* dp, void* stream) {
-  if (!dp) return ADP_ERR_NULL;
-  const adp_conv_desc& d = *dp;
-  if (!d.x || !d.w || !d.out) return ADP_ERR_NULL;
-  if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0 || d.up < 1 || d.R1 < 0 || d.R1 > d.R)
-    return ADP_ERR_SHAPE;
+// Validation both descriptor types share, in the order of precedence of the error codes: the operands (`operands`: the type's
+// own pointers are all set) and extents, then the layer described
+template <class D> int operands_check(const D& d, bool operands) {
+  if (!operands) return ADP_ERR_NULL;
+  if (!dims_ok(d) || d.up < 1 || d.R1 < 0 || d.R1 > d.R) return ADP_ERR_SHAPE;
+  return ADP_OK;
+}
+template <class D> int layer_check(const D& d) {
   if (d.R1 < d.R && !d.x2) return ADP_ERR_NULL;
   if (d.dil < 1 || d.dil > DILMAX) return ADP_ERR_UNSUPPORTED;
   if (!ks_supported(d.KT, d.stride)) return ADP_ERR_UNSUPPORTED;
   if (d.prologue < 0 || d.prologue > 2 || (d.prologue != 0 && !d.pro_stats)) return ADP_ERR_NULL;
   if (d.prologue == 1 && (d.groups < 1 || d.R % d.groups != 0)) return ADP_ERR_SHAPE;
+  return ADP_OK;
+}
+
+int64_t conv_gnb_entries(const adp_conv_desc& d) {
+  if (d.store != 0) return 0;
+  // every family reads gnb_x with 16-byte loads next to its output tile: an address that does not allow them has no such
+  // epilogue (the caller's GroupNorm backward then runs its own first stage)
+  if (reinterpret_cast<uintptr_t>(d.gnb_x) & 15) return 0;
+  const adp_conv_family& f = conv_family(d);
+  return f.gnb_entries ? f.gnb_entries(d) : 0;
+}
+
+int conv_desc_check(const adp_conv_desc& d) {
+  if (const int rc = operands_check(d, d.x && d.w && d.out)) return rc;
+  if (const int rc = layer_check(d)) return rc;
   if (d.store < 0 || d.store > 2 || (d.out_pre && d.store != 0)) return ADP_ERR_UNSUPPORTED;
   if (d.store == 1 && (d.sp < 1 || d.M % d.sp != 0)) return ADP_ERR_SHAPE;
   if (d.store == 2 && ((d.sp != 2 && d.sp != 4) || d.N % d.sp != 0 || d.bias)) return ADP_ERR_UNSUPPORTED;
@@ -857,134 +917,93 @@ extern "C" int adp_conv1d(const adp_conv_desc* dp, void* stream) {
     if (!d.gnb_x || !d.gnb_stats || !d.gnb_gamma || !d.gnb_beta) return ADP_ERR_NULL;
     if (d.gnb_groups < 1 || d.M % d.gnb_groups != 0) return ADP_ERR_SHAPE;
     if (reinterpret_cast<uintptr_t>(d.gnb_ab) & 7) return ADP_ERR_ALIGN;  // (every family stores its (a, b) pairs as 8 bytes: adp.h)
-    if (adp_conv1d_gnb_entries(dp) <= 0) return ADP_ERR_UNSUPPORTED;
+    if (conv_gnb_entries(d) <= 0) return ADP_ERR_UNSUPPORTED;
   }
-  if (adp_conv_tile_eligible(d)) return adp_conv_tile(d, stream);
-  if (adp_conv_tilek_eligible(d)) return adp_conv_tilek(d, stream);
-  if (adp_conv_mm4_eligible(d)) return adp_conv_mm4(d, stream);
-  if (adp_conv_tilek1_eligible(d)) return adp_conv_tilek1(d, stream);
-  if (adp_conv_mm_eligible(d)) return adp_conv_mm(d, stream);
-  if (adp_conv_direct_eligible(d)) return adp_conv_direct(d, stream);
-  if (d.KT == 1) return dispatch_conv<1, 1>(d, stream);
-  if (d.KT == 2) return dispatch_conv<2, 2>(d, stream);
-  if (d.KT == 3) return dispatch_conv<3, 1>(d, stream);
-  return dispatch_conv<4, 4>(d, stream);
+  return ADP_OK;
+}
+
+int wgrad_operands_check(const adp_wgrad_desc& d) { return operands_check(d, d.x && d.dy && d.dw && d.ws); }
+int wgrad_desc_check(const adp_wgrad_desc& d) {
+  if (const int rc = wgrad_operands_check(d)) return rc;
+  if (const int rc = layer_check(d)) return rc;
+  if (adp_cdiv(d.M, 32) > 65535 || adp_cdiv(d.R, 32) > 65535) return ADP_ERR_SHAPE;
+  return ADP_OK;
+}
+
+}  // namespace
+
+extern "C" int adp_conv1d(const adp_conv_desc* dp, void* stream) {
+  if (!dp) return ADP_ERR_NULL;
+  if (const int rc = conv_desc_check(*dp)) return rc;
+  return conv_family(*dp).launch(*dp, stream);
 }
 
 extern "C" int64_t adp_conv1d_ws_bytes(const adp_conv_desc* dp) {
   if (!dp) return ADP_ERR_NULL;
   const adp_conv_desc& d = *dp;
-  if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0) return ADP_ERR_SHAPE;
-  if (adp_conv_tile_eligible(d) || adp_conv_tilek_eligible(d)) return 0;  // (tilek: the K split stays inside the workgroup)
-  if (adp_conv_mm4_eligible(d)) {
-    const int64_t ks4 = adp_conv_mm4_ksplit(d);
-    return ks4 > 1 ? ks4 * d.B * d.M * d.N * (int64_t)sizeof(float) : 0;
-  }
-  if (adp_conv_tilek1_eligible(d)) return 0;  // (its K split stays inside the workgroup)
-  if (!adp_conv_mm_eligible(d)) return 0;
-  const int64_t ks = adp_conv_mm_ksplit(d);
+  if (!dims_ok(d)) return ADP_ERR_SHAPE;
+  const adp_conv_family& f = conv_family(d);
+  const int64_t ks = f.ksplit ? f.ksplit(d) : 1;  // (the potential split: the launch takes it once d.ws is set)
   return ks > 1 ? ks * d.B * d.M * d.N * (int64_t)sizeof(float) : 0;
 }
 
 extern "C" int64_t adp_conv1d_gn_entries(const adp_conv_desc* dp) {
   if (!dp) return ADP_ERR_NULL;
   const adp_conv_desc& d = *dp;
-  if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0) return ADP_ERR_SHAPE;
+  if (!dims_ok(d)) return ADP_ERR_SHAPE;
   if (d.store != 0 || d.M % 4 != 0) return 0;
-  if (adp_conv_tile_eligible(d)) return adp_conv_tile_gn_entries(d);
-  if (adp_conv_tilek_eligible(d)) return adp_conv_tilek_gn_entries(d);
-  if (adp_conv_mm4_eligible(d)) return adp_conv_mm4_gn_entries(d);
-  if (adp_conv_tilek1_eligible(d)) return adp_conv_tilek1_gn_entries(d);
-  // (the K split only happens when the caller passed its scratch: set d.ws before asking)
-  if (adp_conv_mm_eligible(d))  // one slice per 64-position tile, or the K-split reduce kernel's slices
-    return d.ws && adp_conv_mm_ksplit(d) > 1 ? adp_conv_splitk_gn_entries(d) : adp_cdiv(d.N, 64);
-  return 0;
+  const adp_conv_family& f = conv_family(d);
+  return f.gn_entries ? f.gn_entries(d) : 0;
 }
 
 extern "C" int64_t adp_conv1d_gnb_entries(const adp_conv_desc* dp) {
   if (!dp) return ADP_ERR_NULL;
-  const adp_conv_desc& d = *dp;
-  if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0) return ADP_ERR_SHAPE;
-  if (d.store != 0) return 0;
-  // every family reads gnb_x with 16-byte loads next to its output tile: an address that does not allow them has no such
-  // epilogue (the caller's GroupNorm backward then runs its own first stage)
-  if (reinterpret_cast<uintptr_t>(d.gnb_x) & 15) return 0;
-  if (adp_conv_tile_eligible(d)) return adp_conv_tile_gnb_entries(d);
-  if (adp_conv_tilek_eligible(d)) return adp_conv_tilek_gnb_entries(d);
-  if (adp_conv_mm4_eligible(d)) return adp_conv_mm4_gnb_entries(d);
-  if (adp_conv_tilek1_eligible(d)) return 0;
-  if (adp_conv_mm_eligible(d)) return d.gn_part ? 0 : adp_conv_mm_gnb_entries(d);
-  return 0;
+  if (!dims_ok(*dp)) return ADP_ERR_SHAPE;
+  return conv_gnb_entries(*dp);
 }
 
-// which tile the dispatcher picks for this problem: BM * 1000 + BN (introspection for profiling / roofline reports)
+// which tile the dispatcher picks for this problem: the family's code (introspection for profiling / roofline reports)
 extern "C" int64_t adp_conv1d_tile(const adp_conv_desc* dp) {
   if (!dp) return ADP_ERR_NULL;
-  if (adp_conv_tile_eligible(*dp)) return 32 * 1000 + 64;   // wave-tile 32-channel kernel: 32 outputs x 64 positions per wave
-  if (adp_conv_tilek_eligible(*dp)) return 48000000 + 64;   // deep-layer wave tiles: 16 / 32 rows x 64 positions, 8 K slices per workgroup
-  if (adp_conv_mm4_eligible(*dp)) return 64000000 + 32 * 1000 + 128;
-  if (adp_conv_tilek1_eligible(*dp)) return 47000000 + 64;  // 1x1 wave tiles: 16 rows x 64 positions, 8 K slices per workgroup  // F(4,3) block: 6 planes x 4 K groups, 32 rows x 128 positions
-  if (adp_conv_mm_eligible(*dp)) return adp_conv_mm_tile(*dp);
-  if (adp_conv_direct_eligible(*dp)) return 8 * 1000 + 999;  // direct VALU kernel: 8 output channels x 1024 positions
-  return pick_tile(*dp);
+  return conv_family(*dp).tile(*dp);
 }
 
 extern "C" int64_t adp_conv1d_wgrad_ws_bytes(const adp_wgrad_desc* dp) {
   if (!dp || !ks_supported(dp->KT, dp->stride) || dp->B <= 0 || dp->N <= 0) return ADP_ERR_UNSUPPORTED;
-  int64_t nsplit;
-  if (adp_wgrad_mm_eligible(*dp)) return adp_wgrad_mm_ws_floats(*dp) * (int64_t)sizeof(float);
-  if (adp_wgrad_direct_eligible(*dp)) return adp_wgrad_direct_ws_floats(*dp) * (int64_t)sizeof(float);
-  if (wgrad_s1_eligible(*dp)) {
-    int64_t CPB, CPS;
-    wgrad_s1_split(*dp, &CPB, &CPS, &nsplit);
-  } else {
-    int64_t PS, SPB;
-    wgrad_split(*dp, wgrad_bkn(dp->stride), &PS, &SPB);
-    nsplit = dp->B * SPB;
-  }
-  return nsplit * (dp->M * dp->R * dp->KT + dp->M) * (int64_t)sizeof(float);
+  return wgrad_family(*dp).ws_floats(*dp) * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t adp_conv1d_wgrad_partials(const adp_wgrad_desc* dp) {
   if (!dp) return ADP_ERR_NULL;
-  if (dp->B <= 0 || dp->R <= 0 || dp->M <= 0 || dp->N <= 0 || dp->Lin <= 0 || dp->up < 1) return ADP_ERR_SHAPE;
-  return adp_wgrad_mm_eligible(*dp) ? adp_wgrad_mm_nsplit(*dp) : 1;  // (only the matrix-core family has a parked form)
+  if (!dims_ok(*dp) || dp->up < 1) return ADP_ERR_SHAPE;
+  const adp_wgrad_family& f = wgrad_family(*dp);
+  return f.partials ? f.partials(*dp) : 1;
 }
 
-extern "C" int adp_wgrad_reduce_batch(const float* const* ws, float* const* dw, float* const* dbias, int64_t n, int64_t nsplit,
-                                      int64_t cnt, int64_t M, int64_t accumulate, void* stream) {
-  if (!ws || !dw) return ADP_ERR_NULL;
-  if (n <= 0 || nsplit < 1 || cnt <= 0 || M <= 0) return ADP_ERR_SHAPE;
-  for (int64_t i = 0; i < n; ++i)
-    if (!ws[i] || !dw[i] || (dbias && !dbias[i])) return ADP_ERR_NULL;
-  for (int64_t i = 0; i < n; i += ADP_WGR_BATCH) {
-    const int k = (int)(n - i < ADP_WGR_BATCH ? n - i : ADP_WGR_BATCH);
-    const int rc = adp_wgrad_reduce_n(ws + i, dw + i, dbias ? dbias + i : nullptr, k, nsplit, cnt, M, (int)(accumulate & 1), stream);
-    if (rc != ADP_OK) return rc;
-  }
-  return ADP_OK;
+extern "C" int adp_conv1d_wgrad(const adp_wgrad_desc* dp, void* stream) {
+  if (!dp) return ADP_ERR_NULL;
+  if (const int rc = wgrad_desc_check(*dp)) return rc;
+  return wgrad_family(*dp).launch(*dp, stream);
 }
-
-extern "C" int adp_conv1d_wgrad(const adp_wgrad_desc* dp, void* stream);
 
 extern "C" int adp_conv1d_wgrad_batch(const adp_wgrad_desc* ds, int64_t n, void* stream) {
   if (!ds) return ADP_ERR_NULL;
   if (n <= 0) return ADP_ERR_SHAPE;
   // one shape: every integer field equal, the same optional pointers present
-  bool same = true, mm = true;
+  bool same = true, batched = true;
   for (int64_t i = 0; i < n; ++i) {
     const adp_wgrad_desc &a = ds[0], &b = ds[i];
     same = same && a.B == b.B && a.R == b.R && a.R1 == b.R1 && a.Lin == b.Lin && a.M == b.M && a.N == b.N && a.KT == b.KT &&
            a.stride == b.stride && a.dil == b.dil && a.pad == b.pad && a.up == b.up && a.prologue == b.prologue &&
            a.groups == b.groups && a.accumulate == b.accumulate && !a.pro_stats == !b.pro_stats &&
            !a.pro_gamma == !b.pro_gamma && !a.pro_beta == !b.pro_beta && !a.dbias == !b.dbias && !a.x2 == !b.x2;
-    if (!b.x || !b.dy || !b.dw || !b.ws) return ADP_ERR_NULL;
-    if (b.B <= 0 || b.R <= 0 || b.M <= 0 || b.N <= 0 || b.Lin <= 0 || b.up < 1 || b.R1 < 0 || b.R1 > b.R) return ADP_ERR_SHAPE;
-    mm = mm && adp_wgrad_mm_eligible(b) && !(b.prologue != 0 && !b.pro_stats) &&
-         !(b.prologue == 1 && (b.groups < 1 || b.R % b.groups != 0));
+    if (const int rc = wgrad_operands_check(b)) return rc;
+    // (an item its family would refuse goes through adp_conv1d_wgrad below, which reports it)
+    batched = batched && wgrad_family(b).launch_n && wgrad_desc_check(b) == ADP_OK;
   }
   if (!same) return ADP_ERR_SHAPE;
-  if (!mm || n == 1) {  // no batched form for this family: one call per item
+  const adp_wgrad_family& f = wgrad_family(ds[0]);
+  if (!batched || n == 1) {  // no batched form for this family: one call per item
     for (int64_t i = 0; i < n; ++i) {
       const int rc = adp_conv1d_wgrad(ds + i, stream);
       if (rc != ADP_OK) return rc;
@@ -993,28 +1012,8 @@ extern "C" int adp_conv1d_wgrad_batch(const adp_wgrad_desc* ds, int64_t n, void*
   }
   for (int64_t i = 0; i < n; i += ADP_WGR_BATCH) {
     const int k = (int)(n - i < ADP_WGR_BATCH ? n - i : ADP_WGR_BATCH);
-    const int rc = adp_wgrad_mm_n(ds + i, k, stream);
+    const int rc = f.launch_n(ds + i, k, stream);
     if (rc != ADP_OK) return rc;
   }
   return ADP_OK;
-}
-
-extern "C" int adp_conv1d_wgrad(const adp_wgrad_desc* dp, void* stream) {
-  if (!dp) return ADP_ERR_NULL;
-  const adp_wgrad_desc& d = *dp;
-  if (!d.x || !d.dy || !d.dw || !d.ws) return ADP_ERR_NULL;
-  if (d.B <= 0 || d.R <= 0 || d.M <= 0 || d.N <= 0 || d.Lin <= 0 || d.up < 1 || d.R1 < 0 || d.R1 > d.R)
-    return ADP_ERR_SHAPE;
-  if (d.R1 < d.R && !d.x2) return ADP_ERR_NULL;
-  if (d.dil < 1 || d.dil > DILMAX) return ADP_ERR_UNSUPPORTED;
-  if (!ks_supported(d.KT, d.stride)) return ADP_ERR_UNSUPPORTED;
-  if (d.prologue < 0 || d.prologue > 2 || (d.prologue != 0 && !d.pro_stats)) return ADP_ERR_NULL;
-  if (d.prologue == 1 && (d.groups < 1 || d.R % d.groups != 0)) return ADP_ERR_SHAPE;
-  if (adp_cdiv(d.M, 32) > 65535 || adp_cdiv(d.R, 32) > 65535) return ADP_ERR_SHAPE;
-  if (adp_wgrad_mm_eligible(d)) return adp_wgrad_mm(d, stream);
-  if (adp_wgrad_direct_eligible(d)) return adp_wgrad_direct(d, stream);
-  if (d.KT == 1) return launch_wgrad<1, 1>(d, stream);
-  if (d.KT == 2) return launch_wgrad<2, 2>(d, stream);
-  if (d.KT == 3) return launch_wgrad<3, 1>(d, stream);
-  return launch_wgrad<4, 4>(d, stream);
 }

@@ -538,7 +538,7 @@ int launch_dc(const adp_conv_desc& d, void* stream) {
 
 }  // namespace
 
-bool adp_conv_direct_eligible(const adp_conv_desc& d) {
+static bool adp_conv_direct_eligible(const adp_conv_desc& d) {
   if (d.dil != 1 || (d.prologue != 0 && d.prologue != 1) || (d.store != 0 && d.store != 2)) return false;
   const bool s1 = d.stride == 1 && (d.KT == 1 || d.KT == 3) && (d.up == 1 || d.up == 2 || d.up == 4);
   const bool down = (d.stride == 2 || d.stride == 4) && d.KT == d.stride && d.up == 1 && d.pad == 0;
@@ -557,7 +557,7 @@ bool adp_conv_direct_eligible(const adp_conv_desc& d) {
   return true;
 }
 
-int adp_conv_direct(const adp_conv_desc& d, void* stream) {
+static int adp_conv_direct(const adp_conv_desc& d, void* stream) {
   if (d.stride == 2) return launch_dc<2, 2, 1>(d, stream);
   if (d.stride == 4) return launch_dc<4, 4, 1>(d, stream);
   if (d.KT == 3) {
@@ -587,4 +587,11 @@ int adp_conv_direct(const adp_conv_desc& d, void* stream) {
   if (d.up == 2) return launch_dc<1, 1, 2>(d, stream);
   if (d.up == 4) return launch_dc<1, 1, 4>(d, stream);
   return launch_dc<1, 1, 1>(d, stream);
+}
+
+const adp_conv_family& adp_family_direct() {
+  static const adp_conv_family f = {
+      "direct", adp_conv_direct_eligible, adp_conv_direct, nullptr, nullptr, nullptr,
+      [](const adp_conv_desc&) -> int64_t { return 8 * 1000 + 999; }};  // 8 output channels x 1024 positions
+  return f;
 }

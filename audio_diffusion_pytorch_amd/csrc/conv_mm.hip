@@ -16,10 +16,7 @@ constexpr int MM_PRO_RMAX = 1024; // channels whose GroupNorm constants fit the 
 // 64 x 64 block tiles (8 MMA waves + 4 loaders) unless that leaves most of the 256 CUs without a block
 // workgroups a launch should have before the larger tile is chosen (ADP_MM_MIN_BLOCKS: tests reach the large-tile
 // variants with small problems through it)
-static int64_t mm_min_blocks() {
-  const char* e = getenv("ADP_MM_MIN_BLOCKS");
-  return e ? atoll(e) : 200;
-}
+static int64_t mm_min_blocks() { return adp_knob("ADP_MM_MIN_BLOCKS", 200); }
 
 bool mm_use64(const adp_conv_desc& d) {
   if (d.M % 64 != 0) return false;
@@ -187,7 +184,8 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_gnb_kernel(adp_conv_de
 int64_t adp_conv_splitk_gn_entries(const adp_conv_desc& d) { return adp_cdiv(d.N, SPLITK_GN_SLICE); }
 
 // slices per row of gnb_ab a conv_mm launch leaves: its 64-position tiles, or the split-K reduce kernel's slices
-int64_t adp_conv_mm_gnb_entries(const adp_conv_desc& d) {
+static int64_t adp_conv_mm_gnb_entries(const adp_conv_desc& d) {
+  if (d.gn_part) return 0;  // (never together with gn_part: a data gradient feeds no GroupNorm forward)
   // (the instantiations that exist: plain Winograd data gradients)
   if (d.store != 0 || !d.transposed || d.KT != 3 || d.prologue != 0 || d.up != 1 || d.stride != 1 || !adp_conv_mm_winograd(d)) return 0;
   if (!adp_gnb_family_on(d.ws && adp_conv_mm_ksplit(d) > 1 ? 32 : 8)) return 0;
@@ -203,13 +201,8 @@ int64_t adp_conv_mm_gnb_entries(const adp_conv_desc& d) {
 // Cross-workgroup K split: when the output tiles alone leave most of the 256 CUs idle (batch-1 deep layers: depth 8
 // has 64 tiles of 32 x 64) the reduction over input channels is cut into 2 / 4 / 8 slices run by separate
 // workgroups (>= 4 chunks of 32 channels each), combined by conv_splitk_reduce_kernel (deterministic order).
-static int64_t env_or(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
-
 int64_t adp_conv_mm_ksplit(const adp_conv_desc& d) {
-  static const bool off = getenv("ADP_MM_NO_KSPLIT") != nullptr;  // A/B switch for kernel work
+  static const bool off = adp_knob_raw("ADP_MM_NO_KSPLIT") != nullptr;  // A/B switch for kernel work (set at all; read once)
   if (off || d.store != 0) return 1;  // pixel-shuffle / pooled stores keep their in-kernel epilogue
   const int64_t bm = mm_use64(d) ? 64 : 32;
   const int64_t blocks = (d.M / bm) * adp_cdiv(d.N, 64 * adp_conv_mm_nsp(d)) * d.B;
@@ -220,8 +213,8 @@ int64_t adp_conv_mm_ksplit(const adp_conv_desc& d) {
   // (batch 1, larger tiles + deeper splits instead, tools/b1_micro.py, forward us incl. the reduce launch: C=1024 L=256
   //  32-row x ks 2 23.5 | 64-row x ks 4 24.1 | 64 x 128 positions x ks 8 29.9 | 64 x 256 x ks 16 38.6; C=512 L=1024 18.2 | 29.0 |
   //  39.1 | 58.9: at batch 1 the small tile with the shallow split wins everywhere -- the knobs below are for that tool)
-  const int64_t target = env_or("ADP_MM_KS_TARGET", 200), ksmax = env_or("ADP_MM_KS_MAX", 8);
-  const int64_t minch = env_or("ADP_MM_KS_MINCH", 4);
+  const int64_t target = adp_knob("ADP_MM_KS_TARGET", 200), ksmax = adp_knob("ADP_MM_KS_MAX", 8);
+  const int64_t minch = adp_knob("ADP_MM_KS_MINCH", 4);
   while (ks < ksmax && blocks * ks < target && nchunks / (ks * 2) >= minch) ks *= 2;
   // the kernel gives slice i the chunks [i * ceil(n / ks), ...): every slice must own at least one (n = 33, ks = 8 would
   // leave the last two slices empty -- they would launch, restage a ghost chunk and park an all-zero partial tile)
@@ -233,19 +226,13 @@ int64_t adp_conv_mm_ksplit(const adp_conv_desc& d) {
 // matrix bound (also the UpsampleItem convs -- the LDS tile holds virtual upsampled positions -- and the pooled-store
 // data gradients of those).  ADP_CONV_WINO (read per call): unset / "1" = this variant for every eligible conv with at
 // least ADP_WINO_MIN_R (default 32) input channels; "0" = direct form everywhere (A/B and the parity tests).
-bool adp_winograd_enabled() {
-  const char* e = getenv("ADP_CONV_WINO");
-  return e == nullptr || e[0] != '0';
-}
-
 bool adp_conv_mm_winograd(const adp_conv_desc& d) {
   if (!adp_winograd_enabled()) return false;
   if (d.KT != 3 || d.stride != 1 || d.dil != 1 || d.pad != 1 || d.R1 != d.R) return false;
   if (d.up != 1 && d.up != 2 && d.up != 4) return false;
   if (d.store != 0 && !(d.store == 2 && (d.sp == 2 || d.sp == 4))) return false;  // plain or pooled store
   if (d.N != d.Lin * d.up || d.N % 4 != 0) return false;
-  const char* mr = getenv("ADP_WINO_MIN_R");
-  const int64_t min_r = mr ? atoll(mr) : 32;  // (round 4: 64 -> 32 is worth 0.03 ms per step at batch 4, 0.015 at batch 1)
+  const int64_t min_r = adp_knob("ADP_WINO_MIN_R", 32);  // (round 4: 64 -> 32 is worth 0.03 ms per step at batch 4, 0.015 at batch 1)
   if (d.R < min_r) return false;
   if ((reinterpret_cast<uintptr_t>(d.out) | reinterpret_cast<uintptr_t>(d.res) | reinterpret_cast<uintptr_t>(d.out_pre) |
        reinterpret_cast<uintptr_t>(d.ws)) & 7)
@@ -260,18 +247,17 @@ bool adp_conv_mm_winograd(const adp_conv_desc& d) {
 // C=512 L=1024 50.5 -> 45.5 (142 TF in direct-form flops).  Batch 1 keeps the 64-position block (grid too small).
 int adp_conv_mm_nsp(const adp_conv_desc& d) {
   if (!(adp_conv_mm_winograd(d) || (d.KT == 1 && d.up == 1)) || !mm_use64(d) || d.stride != 1) return 1;
-  const char* e = getenv("ADP_MM_NSP");
-  int want = e ? atoi(e) : 4;
+  int want = (int)adp_knob("ADP_MM_NSP", 4);
   // the 1x1 convs are short of work per byte, not of weight reuse (tools/nsp_micro2.py, batch 4, 64 / 128 / 256 positions:
   // 64 -> 128 channels at L = 16384 40.4 / 36.4 / 49.9 us, 256 -> 256 at L = 2048 20.0 / 22.3 / 22.2): 128 positions up to
   // 128 input channels, the 64-position block above; the upsample convs gain like the plain ones (512 -> 256 x2: 49.8 -> 43.7)
   if (d.KT == 1 && want > 1) want = d.R <= 128 ? 2 : 1;
-  const int64_t nsp_min = env_or("ADP_MM_NSP_MIN_BLOCKS", mm_min_blocks());
+  const int64_t nsp_min = adp_knob("ADP_MM_NSP_MIN_BLOCKS", mm_min_blocks());
   while (want > 1 && (d.M / 64) * adp_cdiv(d.N, 64 * want) * d.B < nsp_min) want /= 2;
   return want < 1 ? 1 : want;
 }
 
-bool adp_conv_mm_eligible(const adp_conv_desc& d) {
+static bool adp_conv_mm_eligible(const adp_conv_desc& d) {
   if (d.R1 != d.R) return false;
   const bool plain = d.stride == 1 && (d.KT == 1 || d.KT == 3) && d.up == 1;                    // ConvBlock family
   const bool upc = d.stride == 1 && d.KT == 3 && (d.up == 2 || d.up == 4) && !d.transposed && d.prologue == 0;
@@ -289,7 +275,7 @@ bool adp_conv_mm_eligible(const adp_conv_desc& d) {
 }
 
 // NKG * 1e6 + BM * 1e3 + BN of the tile the dispatcher picks
-int64_t adp_conv_mm_tile(const adp_conv_desc& d) {
+static int64_t adp_conv_mm_tile(const adp_conv_desc& d) {
   const int64_t nkg = d.stride == 4 ? 2 : 4;
   const int64_t nsp = adp_conv_mm_nsp(d);
   return (adp_conv_mm_winograd(d) ? 40000000 : 0) + (nkg / nsp) * 1000000 + (mm_use64(d) ? 64000 : 32000) + 64 * nsp;
@@ -313,9 +299,21 @@ int adp_conv_splitk_reduce(const adp_conv_desc& d, int64_t ks, void* stream) {
   return ADP_LAUNCH_OK();
 }
 
-int adp_conv_mm(const adp_conv_desc& d, void* stream) {
+static int adp_conv_mm(const adp_conv_desc& d, void* stream) {
   const int rc = mm_use64(d) ? adp_conv_mm_m64(d, stream) : adp_conv_mm_m32(d, stream);
   const int64_t ks = d.ws ? adp_conv_mm_ksplit(d) : 1;
   if (rc == ADP_OK && ks > 1) return adp_conv_splitk_reduce(d, ks, stream);
   return rc;
+}
+
+// gn_part slices per row quad: one per 64-position tile, or the K-split reduce kernel's slices (the K split only happens when
+// the caller passed its scratch: set d.ws before asking)
+static int64_t adp_conv_mm_gn_entries(const adp_conv_desc& d) {
+  return d.ws && adp_conv_mm_ksplit(d) > 1 ? adp_conv_splitk_gn_entries(d) : adp_cdiv(d.N, 64);
+}
+
+const adp_conv_family& adp_family_mm() {
+  static const adp_conv_family f = {"mm", adp_conv_mm_eligible, adp_conv_mm, adp_conv_mm_ksplit, adp_conv_mm_gn_entries,
+                                         adp_conv_mm_gnb_entries, adp_conv_mm_tile};
+  return f;
 }

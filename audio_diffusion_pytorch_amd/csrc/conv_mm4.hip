@@ -676,34 +676,27 @@ __global__ __launch_bounds__((M4_NKG * NPG + M4_NLD) * 64, (M4_NKG == 2 && BKT =
   ADP_KT_DUMP(blockIdx.x);
 }
 
-int64_t m4_min_blocks() {
-  const char* e = getenv("ADP_MM4_MIN_BLOCKS");  // (the tests reach this block with small problems through it)
-  return e ? atoll(e) : 200;
-}
+int64_t m4_min_blocks() { return adp_knob("ADP_MM4_MIN_BLOCKS", 200); }  // (the tests reach this block with small problems through it)
 
 }  // namespace
 
-int64_t adp_conv_mm4_ksplit(const adp_conv_desc& d);
+static int64_t adp_conv_mm4_ksplit(const adp_conv_desc& d);
 
 // ADP_CONV_WINO4 (read per call): unset / "1" = this kernel for every eligible conv; "0" = conv_mm's F(2,3) variant (A/B, tests)
-bool adp_conv_mm4_eligible(const adp_conv_desc& d) {
+static bool adp_conv_mm4_eligible(const adp_conv_desc& d) {
   if (!adp_winograd_enabled()) return false;
-  const char* e = getenv("ADP_CONV_WINO4");
-  if (e && e[0] == '0') return false;
+  if (!adp_knob_on("ADP_CONV_WINO4")) return false;
   if (d.KT != 3 || d.stride != 1 || d.dil != 1 || d.pad != 1 || d.R1 != d.R || d.x2) return false;
   if (d.up != 1 && !((d.up == 2 || d.up == 4) && !d.transposed && d.store == 0)) return false;   // UpsampleItem conv (forward)
   if (d.prologue != 0) return false;
   if (d.store != 0 && !(d.store == 2 && (d.sp == 2 || d.sp == 4) && d.up == 1 && !d.bias && !d.e_scale && !d.out_pre))
     return false;  // plain store, or the pooled store of the UpsampleItem convs' data gradients
   if (d.N != d.Lin * d.up || d.N % 4 != 0) return false;
-  {
-    const char* eu = getenv("ADP_MM4_UP");  // (A/B: "0" keeps the UpsampleItem convs and their data gradients on conv_mm)
-    if (eu && eu[0] == '0' && (d.up != 1 || d.store != 0)) return false;
-  }
-  const char* mr = getenv("ADP_WINO4_MIN_R");
+  // (A/B: ADP_MM4_UP=0 keeps the UpsampleItem convs and their data gradients on conv_mm)
+  if (!adp_knob_on("ADP_MM4_UP") && (d.up != 1 || d.store != 0)) return false;
   // (from 128 channels: the materialised-activation layers; with the 12-wave block only, the short-K layers of depths 3-4 lost
   //  to conv_mm's wide-N F(2,3) blocks -- 12.22 vs 12.15 ms per step -- the light block wins them back: m4_nkg)
-  if (d.R < (mr ? atoll(mr) : 64) || d.R % 32 != 0 || d.M % M4_BM != 0) return false;  // (round 6: from 64 channels)
+  if (d.R < adp_knob("ADP_WINO4_MIN_R", 64) || d.R % 32 != 0 || d.M % M4_BM != 0) return false;  // (round 6: from 64 channels)
   if ((reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.w) | reinterpret_cast<uintptr_t>(d.out) |
        reinterpret_cast<uintptr_t>(d.res) | reinterpret_cast<uintptr_t>(d.out_pre)) & 15)
     return false;
@@ -716,18 +709,14 @@ bool adp_conv_mm4_eligible(const adp_conv_desc& d) {
 // layers of depth 8 are 128 tiles.  OFF by default (ADP_MM4_KS_MAX=2 / 4 switches it on): measured at batch 4 it is worth
 // 12.16 -> 12.11 ms and 11.90 -> 11.875 ms per step (the reduce launch eats most of what the matrix cores save) for 32 more
 // launches per step; depth 8 stays on conv_mm's 64-position F(2,3) blocks.
-int64_t adp_conv_mm4_ksplit(const adp_conv_desc& d) {
-  const char* e = getenv("ADP_MM4_KS_MAX");
-  const int64_t ksmax = e ? atoll(e) : 1;
+static int64_t adp_conv_mm4_ksplit(const adp_conv_desc& d) {
+  const int64_t ksmax = adp_knob("ADP_MM4_KS_MAX", 1);
   const int64_t blocks = (d.M / M4_BM) * adp_cdiv(d.N, M4_BN) * d.B, nchunks = d.R / 64;
   if (d.store != 0 || d.up != 1) return 1;  // (the pooled store and the upsample loader keep their in-kernel epilogue)
   int64_t ks = 1;
   // (every slice keeps >= 8 chunks of 64 channels: at batch 1 the 512-channel layers would qualify with 4 and lose to conv_mm's
   //  64-position blocks -- batch-1 step 6.46 -> 6.53 ms; depth 8 at batch 4: step 12.16 -> 12.11 ms)
-  const char* mc = getenv("ADP_MM4_KS_MINCH");
-  const int64_t minch = mc ? atoll(mc) : 8;
-  const char* tg = getenv("ADP_MM4_KS_TARGET");
-  const int64_t target = tg ? atoll(tg) : m4_min_blocks();
+  const int64_t minch = adp_knob("ADP_MM4_KS_MINCH", 8), target = adp_knob("ADP_MM4_KS_TARGET", m4_min_blocks());
   while (ks < ksmax && blocks * ks < target && d.R % 64 == 0 && nchunks / (ks * 2) >= minch) ks *= 2;
   return ks;
 }
@@ -741,13 +730,12 @@ int64_t adp_conv_mm4_ksplit(const adp_conv_desc& d) {
 static int64_t m4_ks_eff(const adp_conv_desc& d) { return d.ws ? adp_conv_mm4_ksplit(d) : 1; }
 
 static bool m4_light(const adp_conv_desc& d) {
-  const char* e = getenv("ADP_MM4_LIGHT_MIN_BLOCKS");
   const int64_t blocks = (d.M / M4_BM) * adp_cdiv(d.N, M4_BN) * d.B * m4_ks_eff(d);
-  return blocks >= (e ? atoll(e) : 400);
+  return blocks >= adp_knob("ADP_MM4_LIGHT_MIN_BLOCKS", 400);
 }
 static int m4_nkg(const adp_conv_desc& d) { return m4_light(d) ? 2 : 4; }
 
-int64_t adp_conv_mm4_gn_entries(const adp_conv_desc& d) {
+static int64_t adp_conv_mm4_gn_entries(const adp_conv_desc& d) {
   if (d.store != 0) return 0;
   if (m4_ks_eff(d) > 1) return adp_conv_splitk_gn_entries(d);
   return (m4_nkg(d) == 2 ? 1 : 2) * adp_cdiv(d.N, M4_BN);
@@ -757,14 +745,14 @@ int64_t adp_conv_mm4_gn_entries(const adp_conv_desc& d) {
 // HBM-bound, the epilogue's read of x costs what the separate first stage's did (measured: conv 24.8 -> 34.8 us for 11.3 saved).
 // Per-launch effect at batch 4 (eager event pairs, us): conv +0 .. +4, second stage +0.6 .. +2.3, first stage's 6.7 .. 8.5 gone;
 // 48 launches less per step, step time within +-0.04 ms (a small kernel costs ~3 us inside the replayed graph).
-int64_t adp_conv_mm4_gnb_entries(const adp_conv_desc& d) {
+static int64_t adp_conv_mm4_gnb_entries(const adp_conv_desc& d) {
   if (d.store != 0 || m4_ks_eff(d) > 1 || !d.transposed || d.up != 1) return 0;  // (the instantiations that exist)
   if (d.M < 128 && d.B * d.M * d.N > (4 << 20)) return 0;
   if (!adp_gnb_family_on(m4_nkg(d) == 2 ? 2 : 1)) return 0;  // (the HBM-bound case above; at batch 1 the tensor is 4 MB and cached)
   return adp_cdiv(d.N, M4_BN);
 }
 
-int adp_conv_mm4(const adp_conv_desc& d, void* stream) {
+static int adp_conv_mm4(const adp_conv_desc& d, void* stream) {
   const int64_t blocks = (d.M / M4_BM) * adp_cdiv(d.N, M4_BN) * d.B;
   const int64_t ks = m4_ks_eff(d);  // (without the caller's scratch: the unsplit path, still correct)
   const dim3 grid((unsigned)blocks, (unsigned)ks);
@@ -783,8 +771,7 @@ int adp_conv_mm4(const adp_conv_desc& d, void* stream) {
     return ADP_LAUNCH_OK();
   }
   // loaders stage the transformed inputs (VPRE) for full 128-position tiles: ADP_MM4_VPRE=0 / 1 (A/B)
-  const char* ev = getenv("ADP_MM4_VPRE");
-  const bool vpre = d.N % M4_BN == 0 && (ev ? ev[0] != '0' : M4_VPRE_DEFAULT);
+  const bool vpre = d.N % M4_BN == 0 && adp_knob_on("ADP_MM4_VPRE", M4_VPRE_DEFAULT);
   if (m4_nkg(d) == 2 && vpre) {
     const dim3 block((2 * M4_NPG + M4_NLD) * 64);
     if (d.transposed && d.gnb_ab) ADP_LAUNCH((conv_mm4_kernel<true, 1, 32, 2, 1, true, 2, true>), grid, block, stream, d);
@@ -803,10 +790,8 @@ int adp_conv_mm4(const adp_conv_desc& d, void* stream) {
   }
   const dim3 block((4 * M4_NPG + M4_NLD) * 64);
   // 64-channel chunks (24 MFMAs per wave and barrier instead of 12) unless ADP_MM4_BKT=32: step 12.15 -> 12.09 ms
-  const char* e = getenv("ADP_MM4_BKT");
-  const int bkt = (e ? atoi(e) : 64) == 64 && d.R % 64 == 0 ? 64 : 32;
-  const char* e3 = getenv("ADP_MM4_NPG");
-  if (bkt == 64 && e3 && atoi(e3) == 3) {  // 16-wave block: three plane groups (see NPG)
+  const int bkt = adp_knob("ADP_MM4_BKT", 64) == 64 && d.R % 64 == 0 ? 64 : 32;
+  if (bkt == 64 && adp_knob("ADP_MM4_NPG", 0) == 3) {  // 16-wave block: three plane groups (see NPG)
     const dim3 block16((4 * 3 + M4_NLD) * 64);
     if (d.transposed && d.gnb_ab) ADP_LAUNCH((conv_mm4_kernel<true, 1, 64, 4, 1, true, 3>), grid, block16, stream, d);
     else if (d.transposed) ADP_LAUNCH((conv_mm4_kernel<true, 1, 64, 4, 1, false, 3>), grid, block16, stream, d);
@@ -835,4 +820,11 @@ int adp_conv_mm4(const adp_conv_desc& d, void* stream) {
   if (ADP_LAUNCH_OK() != ADP_OK) return ADP_ERR_LAUNCH;
   if (ks > 1) return adp_conv_splitk_reduce(d, ks, stream);
   return ADP_OK;
+}
+
+const adp_conv_family& adp_family_mm4() {
+  static const adp_conv_family f = {
+      "mm4", adp_conv_mm4_eligible, adp_conv_mm4, adp_conv_mm4_ksplit, adp_conv_mm4_gn_entries, adp_conv_mm4_gnb_entries,
+      [](const adp_conv_desc&) -> int64_t { return 64000000 + 32 * 1000 + 128; }};  // F(4,3) block: 6 planes x 4 K groups, 32 rows x 128 positions
+  return f;
 }

@@ -636,8 +636,7 @@ int launch_mm(const adp_conv_desc& d, void* stream) {
   // sampler 2.407 -> 2.383 (ADP_MM_PF=0/1 interleaved on one box).  The 12-wave 64-row blocks (two MMA waves per SIMD hide each
   // other's reads) lose with it: 13.16 -> 13.27 ms.
   if constexpr (WN && BM == 32 && NSP == 1 && BKT == 32 && UP == 1 && mm_nld(PRO, BM, PD, NSP) == 4) {
-    const char* e = getenv("ADP_MM_PF");
-    if (!e || e[0] != '0') {
+    if (adp_knob_on("ADP_MM_PF")) {
       ADP_LAUNCH((conv_mm_kernel<BM, KT, S, UP, TR, PRO, BKT, PD, WN, NSP, true, GNB>), dim3((unsigned)blocks, (unsigned)KS),
                  dim3(((BM / 32) * mm_nkg(BKT) + mm_nld(PRO, BM, PD, NSP)) * 64), stream, d, KS);
       return ADP_LAUNCH_OK();
@@ -697,11 +696,8 @@ int run_tile(const adp_conv_desc& d, void* stream) {
   // 1x1 convs (the DownsampleItem data gradients as a 1x1 over the space-to-depth view, attention projections): one tap per
   // channel pair = 8 MFMAs per wave and barrier with 32-channel chunks -- 64-channel chunks halve the barriers per MFMA
   // (ADP_MM_K1_BKT=32: the old chunk; not with the cross-workgroup K split, whose slices are counted in 32-channel chunks)
-  {
-    const char* e = getenv("ADP_MM_K1_BKT");
-    if ((!e || atoi(e) == 64) && d.R % 64 == 0 && d.R >= 256 && (!d.ws || adp_conv_mm_ksplit(d) == 1))
-      return tr ? launch_pd<BM, 1, 1, 1, true, 0, 64>(d, stream) : launch_pd<BM, 1, 1, 1, false, 0, 64>(d, stream);
-  }
+  if (adp_knob("ADP_MM_K1_BKT", 64) == 64 && d.R % 64 == 0 && d.R >= 256 && (!d.ws || adp_conv_mm_ksplit(d) == 1))
+    return tr ? launch_pd<BM, 1, 1, 1, true, 0, 64>(d, stream) : launch_pd<BM, 1, 1, 1, false, 0, 64>(d, stream);
   return tr ? launch_pd<BM, 1, 1, 1, true, 0, 32>(d, stream) : launch_pd<BM, 1, 1, 1, false, 0, 32>(d, stream);
 }
 

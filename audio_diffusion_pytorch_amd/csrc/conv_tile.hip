@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64 * NW) void conv_tile32_kernel(adp_conv_desc d, i
 // grids; the workgroup's tiles must lie in one batch element
 static int tile_nw(const adp_conv_desc& d) {
   const int64_t tiles_per_b = d.N / WT_TN, tiles = tiles_per_b * d.B;
-  const char* e = getenv("ADP_TILE_NW");  // tests: every variant on small problems
+  const char* e = adp_knob_raw("ADP_TILE_NW");  // tests: every variant on small problems (set at all: no minimum grid)
   const int want = e ? atoi(e) : 16;
   for (int nw : {16, 4})
     if (nw <= want && tiles_per_b % nw == 0 && (e || tiles / nw >= 256)) return nw;
@@ -374,8 +374,8 @@ int launch_tile(const adp_conv_desc& d, void* stream) {
   const int tiles_per_b = (int)(d.N / WT_TN);
   const int nw = tile_nw(d);
   const unsigned grid = (unsigned)(d.B * tiles_per_b / nw);
-  int cfg = 120;  // stagger between the wave stages: 1.2 us
-  if (const char* e = getenv("ADP_TILE_CFG")) cfg = atoi(e);  // kernel work: gap | elimination bits << 16 (probe builds)
+  // stagger between the wave stages: 1.2 us (ADP_TILE_CFG, kernel work: gap | elimination bits << 16 in probe builds)
+  const int cfg = (int)adp_knob("ADP_TILE_CFG", 120);
   switch (nw) {
     case 16: ADP_LAUNCH((conv_tile32_kernel<TR, PRO, 16, RES, GN>), dim3(grid), dim3(1024), stream, d, tiles_per_b, cfg); break;
     case 4: ADP_LAUNCH((conv_tile32_kernel<TR, PRO, 4, RES, GN>), dim3(grid), dim3(256), stream, d, tiles_per_b, cfg); break;
@@ -410,7 +410,7 @@ int launch_tile2(const adp_conv_desc& d, void* stream) {
 
 }  // namespace
 
-bool adp_conv_tile_eligible(const adp_conv_desc& d) {
+static bool adp_conv_tile_eligible(const adp_conv_desc& d) {
   if (d.R != WT_C || d.R1 != d.R || d.M != WT_C || d.KT != WT_KT) return false;
   if (d.stride != 1 || d.dil != 1 || d.pad != 1 || d.up != 1 || d.store != 0) return false;
   if (d.out_pre || d.e_scale || d.x2) return false;
@@ -425,12 +425,19 @@ bool adp_conv_tile_eligible(const adp_conv_desc& d) {
   return true;
 }
 
-int64_t adp_conv_tile_gn_entries(const adp_conv_desc& d) { return d.N / WT_TN / tile_nw(d); }
+static int64_t adp_conv_tile_gn_entries(const adp_conv_desc& d) { return d.N / WT_TN / tile_nw(d); }
 // slices per row of gnb_ab: one per workgroup (plain data gradients only; gnb_x / gamma / beta 16-byte aligned)
-int64_t adp_conv_tile_gnb_entries(const adp_conv_desc& d) { return tile_gnb_ok(d) && adp_gnb_family_on(16) ? d.N / WT_TN / tile_nw(d) : 0; }
+static int64_t adp_conv_tile_gnb_entries(const adp_conv_desc& d) { return tile_gnb_ok(d) && adp_gnb_family_on(16) ? d.N / WT_TN / tile_nw(d) : 0; }
 
-int adp_conv_tile(const adp_conv_desc& d, void* stream) {
+static int adp_conv_tile(const adp_conv_desc& d, void* stream) {
   if (d.gnb_ab) return launch_tile_gnb(d, stream);  // (adp_conv1d has checked adp_conv_tile_gnb_entries)
   if (d.transposed) return d.prologue == 1 ? launch_tile2<true, 1>(d, stream) : launch_tile2<true, 0>(d, stream);
   return d.prologue == 1 ? launch_tile2<false, 1>(d, stream) : launch_tile2<false, 0>(d, stream);
+}
+
+const adp_conv_family& adp_family_tile() {
+  static const adp_conv_family f = {
+      "tile", adp_conv_tile_eligible, adp_conv_tile, nullptr, adp_conv_tile_gn_entries, adp_conv_tile_gnb_entries,
+      [](const adp_conv_desc&) -> int64_t { return 32 * 1000 + 64; }};  // 32 outputs x 64 positions per wave
+  return f;
 }

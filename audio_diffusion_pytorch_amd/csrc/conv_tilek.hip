@@ -334,7 +334,7 @@ static int64_t tilek_tiles32(const adp_conv_desc& d) { return (d.M / 32) * d.B *
 
 // row blocks per tile: 32-row tiles when they alone give every CU a workgroup, else 16-row tiles (twice the workgroups)
 static int tilek_rb(const adp_conv_desc& d) {
-  const char* e = getenv("ADP_TILEK_RB");  // tests / A-B: force 1 or 2
+  const char* e = adp_knob_raw("ADP_TILEK_RB");  // tests / A-B: force 1 or 2
   if (e && (e[0] == '1' || e[0] == '2')) return e[0] - '0';
   return tilek_tiles32(d) >= 200 ? 2 : 1;
 }
@@ -344,10 +344,9 @@ int launch_tilek(const adp_conv_desc& d, void* stream) {
   const int ntn = (int)(d.N / TK_TN);
   const unsigned grid = (unsigned)((d.M / (16 * RB)) * d.B * ntn);
   const int64_t nch = d.R / TK_NKW / TK_CH;
-  const char* pf = getenv("ADP_TILEK_PF");
   // chunks in flight per wave: 2.  In-step A/B (hipGraph replay, same box), 2 -> 4: batch-1 step 6.22 -> 6.28 ms, config-4 layout
   // 10.12 -> 10.19 ms -- the CUs are short of L1 fill rate, not of requests in flight (ADP_TILEK_PF=4: the deeper variant, 16-row tiles)
-  const bool pf4 = RB == 1 && pf && atoi(pf) == 4;
+  const bool pf4 = RB == 1 && adp_knob("ADP_TILEK_PF", 2) == 4;
   if constexpr (TR) {
     if (d.gnb_ab) {
       if (nch == 4) ADP_LAUNCH((conv_tilek_kernel<TR, RB, 4, 2, true>), dim3(grid), dim3(64 * TK_NKW), stream, d, ntn);
@@ -369,21 +368,17 @@ int launch_tilek(const adp_conv_desc& d, void* stream) {
 // Taken where the output tiles alone leave the chip short of work (ADP_TILEK_MIN_TILES .. ADP_TILEK_MAX_TILES 32-row tiles,
 // default 100 .. 320: depths 5-7 at batch 1, depth 8 at batch 2-4) and the K loop is long enough to split eight ways in 16-channel chunks (ADP_TILEK_MIN_R, 512).
 // ADP_CONV_TILEK=0: those layers stay on conv_mm / conv_mm4 with their cross-workgroup K split (A/B).
-bool adp_conv_tilek_eligible(const adp_conv_desc& d) {
+static bool adp_conv_tilek_eligible(const adp_conv_desc& d) {
   if (!adp_winograd_enabled()) return false;
-  const char* e = getenv("ADP_CONV_TILEK");
-  if (e && e[0] == '0') return false;
+  if (!adp_knob_on("ADP_CONV_TILEK")) return false;
   if (d.KT != TK_KT || d.stride != 1 || d.dil != 1 || d.pad != 1 || d.up != 1 || d.store != 0) return false;
   if (d.prologue != 0 || d.x2 || d.R1 != d.R || d.out_pre || d.e_scale) return false;
-  const char* mr = getenv("ADP_TILEK_MIN_R");
-  if (d.R < (mr ? atoll(mr) : 512) || d.R % (2 * TK_NKW * TK_CH) != 0 || d.M % 32 != 0) return false;  // (chunk pairs)
+  if (d.R < adp_knob("ADP_TILEK_MIN_R", 512) || d.R % (2 * TK_NKW * TK_CH) != 0 || d.M % 32 != 0) return false;  // (chunk pairs)
   if (d.N != d.Lin || d.N % TK_TN != 0) return false;
   // hipGraph microbench, us per launch (conv2 + residual; mm = conv_mm / conv_mm4 incl. its reduce launch -> this kernel):
   //   [1,512,1024] 17.4 -> 16.4 (32-row)   [1,512,512] 12.7 -> 10.0   [1,1024,256] 19.3 -> 16.5   [2,1024,128] 18.8 -> 16.1 (16-row)
   //   [4,1024,128] 28.4 -> 25.9 (32-row; data gradient 28.0 -> 22.1)    [1,1024,128] 13.6 -> 15.7 and [8,1024,128] 40 -> 38: left out
-  const char* mt = getenv("ADP_TILEK_MAX_TILES");
-  const char* mn = getenv("ADP_TILEK_MIN_TILES");
-  if (tilek_tiles32(d) > (mt ? atoll(mt) : 320) || tilek_tiles32(d) < (mn ? atoll(mn) : 100)) return false;
+  if (tilek_tiles32(d) > adp_knob("ADP_TILEK_MAX_TILES", 320) || tilek_tiles32(d) < adp_knob("ADP_TILEK_MIN_TILES", 100)) return false;
   if ((reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.w) | reinterpret_cast<uintptr_t>(d.out) |
        reinterpret_cast<uintptr_t>(d.res)) & 15)
     return false;
@@ -392,11 +387,18 @@ bool adp_conv_tilek_eligible(const adp_conv_desc& d) {
   return true;
 }
 
-int64_t adp_conv_tilek_gn_entries(const adp_conv_desc& d) { return d.N / TK_TN; }
+static int64_t adp_conv_tilek_gn_entries(const adp_conv_desc& d) { return d.N / TK_TN; }
 // one slice per row and 64-position tile (data gradients: the instantiations that exist)
-int64_t adp_conv_tilek_gnb_entries(const adp_conv_desc& d) { return d.transposed && adp_gnb_family_on(4) ? d.N / TK_TN : 0; }
+static int64_t adp_conv_tilek_gnb_entries(const adp_conv_desc& d) { return d.transposed && adp_gnb_family_on(4) ? d.N / TK_TN : 0; }
 
-int adp_conv_tilek(const adp_conv_desc& d, void* stream) {
+static int adp_conv_tilek(const adp_conv_desc& d, void* stream) {
   if (tilek_rb(d) == 2) return d.transposed ? launch_tilek<true, 2>(d, stream) : launch_tilek<false, 2>(d, stream);
   return d.transposed ? launch_tilek<true, 1>(d, stream) : launch_tilek<false, 1>(d, stream);
+}
+
+const adp_conv_family& adp_family_tilek() {
+  static const adp_conv_family f = {  // (no ksplit: the K split stays inside the workgroup)
+      "tilek", adp_conv_tilek_eligible, adp_conv_tilek, nullptr, adp_conv_tilek_gn_entries, adp_conv_tilek_gnb_entries,
+      [](const adp_conv_desc&) -> int64_t { return 48000000 + 64; }};  // 16 / 32 rows x 64 positions, 8 K slices per workgroup
+  return f;
 }

@@ -199,27 +199,22 @@ int64_t tilek1_tiles(const adp_conv_desc& d) { return (d.M / 16) * d.B * (d.N / 
 }  // namespace
 
 // Taken where 16-row tiles fill the chip at most about twice (conv_mm splits K across workgroups below ~200 of its blocks): ADP_CONV_TILEK1=0 switches it off (A/B, tests), ADP_TILEK1_MIN_R / _MAX_TILES / _MIN_TILES move the window.
-bool adp_conv_tilek1_eligible(const adp_conv_desc& d) {
-  const char* e = getenv("ADP_CONV_TILEK1");
-  if (e && e[0] == '0') return false;
+static bool adp_conv_tilek1_eligible(const adp_conv_desc& d) {
+  if (!adp_knob_on("ADP_CONV_TILEK1")) return false;
   if (d.KT != 1 || d.stride != 1 || d.dil != 1 || d.pad != 0 || d.up != 1) return false;
   if (d.store != 0 && !(d.store == 1 && d.transposed && !d.gn_part && d.sp >= 1 && d.M % d.sp == 0)) return false;  // (SH instantiation)
   if (d.prologue != 0 || d.x2 || d.R1 != d.R || d.out_pre || d.e_scale || d.gnb_ab) return false;
-  const char* mr = getenv("ADP_TILEK1_MIN_R");
-  const char* xr = getenv("ADP_TILEK1_MAX_R");  // (2048 channels = 16 serial chunks per wave: conv_mm's split wins, 15.2 vs 18.3 us)
-  if (d.R < (mr ? atoll(mr) : 256) || d.R > (xr ? atoll(xr) : 1024) || d.R % (2 * T1_NKW * T1_CH) != 0 || d.M % 16 != 0) return false;
+  // (ADP_TILEK1_MAX_R: 2048 channels = 16 serial chunks per wave: conv_mm's split wins, 15.2 vs 18.3 us)
+  if (d.R < adp_knob("ADP_TILEK1_MIN_R", 256) || d.R > adp_knob("ADP_TILEK1_MAX_R", 1024) || d.R % (2 * T1_NKW * T1_CH) != 0 || d.M % 16 != 0) return false;
   if (d.gn_part && d.M % 4 != 0) return false;
   if (d.N != d.Lin || d.N % T1_TN != 0) return false;
-  const char* mt = getenv("ADP_TILEK1_MAX_TILES");
-  const char* mn = getenv("ADP_TILEK1_MIN_TILES");
   const int64_t tiles = tilek1_tiles(d);
-  if (tiles > (mt ? atoll(mt) : 512) || tiles < (mn ? atoll(mn) : 32)) return false;
+  if (tiles > adp_knob("ADP_TILEK1_MAX_TILES", 512) || tiles < adp_knob("ADP_TILEK1_MIN_TILES", 32)) return false;
   // hipGraph microbench (tools/tilek1_micro.py), us per launch, conv_mm (incl. its reduce launch) -> this kernel, forward + residual /
   // data gradient: [1,512->512,512] 11.1 / 10.7 -> 6.3 / 6.3; [1,1024->512,128] 10.6 / 9.4 -> 8.8 / 6.3; [1,512->1024,256] 10.9 /
   // 11.0 -> 6.1 / 9.2; [1,512->512,1024] (no K split in conv_mm) 14.9 / 12.2 -> 10.4 / 10.1; [4,1024->512,128] 14.9 / 11.8 -> 9.3 / 9.9;
   // beyond 512 tiles: [4,512->512,512] 20.0 / 17.2 -> 19.2 / 19.7, [1,256->512,2048] 14.2 / 12.3 -> 12.3 / 12.1: left to conv_mm
-  const char* mb = getenv("ADP_TILEK1_MM_BLOCKS");  // (A/B: only where conv_mm has fewer blocks than this)
-  if (mb && (d.M / 32) * (d.N / 64) * d.B >= atoll(mb)) return false;
+  if ((d.M / 32) * (d.N / 64) * d.B >= adp_knob("ADP_TILEK1_MM_BLOCKS", INT64_MAX)) return false;  // (A/B: only where conv_mm has fewer blocks than this)
   if ((reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.w) | reinterpret_cast<uintptr_t>(d.out) |
        reinterpret_cast<uintptr_t>(d.res)) & 15)
     return false;
@@ -228,15 +223,14 @@ bool adp_conv_tilek1_eligible(const adp_conv_desc& d) {
   return true;
 }
 
-int64_t adp_conv_tilek1_gn_entries(const adp_conv_desc& d) { return d.N / T1_TN; }
+static int64_t adp_conv_tilek1_gn_entries(const adp_conv_desc& d) { return d.N / T1_TN; }
 
-int adp_conv_tilek1(const adp_conv_desc& d, void* stream) {
+static int adp_conv_tilek1(const adp_conv_desc& d, void* stream) {
   const int ntn = (int)(d.N / T1_TN);
   const unsigned grid = (unsigned)((d.M / 16) * d.B * ntn);
   // ADP_TILEK1_NKW=16 (A/B, tests): sixteen K slices, four waves per SIMD.  Measured 0.5-0.8 us SLOWER per launch on every shape
   // ([1,1024->512,128] 8.8 -> 9.6 us, [1,512->512,512] 6.3 -> 6.8): the K loop is not what these launches wait for.  Default: eight.
-  const char* e = getenv("ADP_TILEK1_NKW");
-  const bool w16 = e && atoi(e) == 16 && d.R % (2 * 16 * T1_CH) == 0 && d.store == 0;
+  const bool w16 = adp_knob("ADP_TILEK1_NKW", 0) == 16 && d.R % (2 * 16 * T1_CH) == 0 && d.store == 0;
   if (w16) {
     if (d.transposed) ADP_LAUNCH((conv_tilek1_kernel<true, 16>), dim3(grid), dim3(64 * 16), stream, d, ntn);
     else ADP_LAUNCH((conv_tilek1_kernel<false, 16>), dim3(grid), dim3(64 * 16), stream, d, ntn);
@@ -246,4 +240,11 @@ int adp_conv_tilek1(const adp_conv_desc& d, void* stream) {
   else if (d.transposed) ADP_LAUNCH((conv_tilek1_kernel<true>), dim3(grid), dim3(64 * T1_NKW), stream, d, ntn);
   else ADP_LAUNCH((conv_tilek1_kernel<false>), dim3(grid), dim3(64 * T1_NKW), stream, d, ntn);
   return ADP_LAUNCH_OK();
+}
+
+const adp_conv_family& adp_family_tilek1() {
+  static const adp_conv_family f = {  // (no ksplit: the K split stays inside the workgroup; no gnb hook: no such instantiation)
+      "tilek1", adp_conv_tilek1_eligible, adp_conv_tilek1, nullptr, adp_conv_tilek1_gn_entries, nullptr,
+      [](const adp_conv_desc&) -> int64_t { return 47000000 + 64; }};  // 16 rows x 64 positions, 8 K slices per workgroup
+  return f;
 }

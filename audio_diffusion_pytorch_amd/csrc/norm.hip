@@ -1144,8 +1144,7 @@ static LnvCfg lnv_cfg(int64_t C, int64_t B, int64_t L, bool bwd = false) {
   if (C <= 64) return {16, 256, 4};    // 256 B, 16 rows per pass
   if (C <= 128) return {8, 256, 4};    // 128 B, 32 rows per pass
   if (C <= 256) {  // 128 B segments; 512 threads x 4 passes (1024 x 2 before round 4: ADP_LNV_NT=1024)
-    const char* e = getenv(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT");
-    if (e && atoi(e) == 1024) return {8, 1024, 2};
+    if (adp_knob(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT", 512) == 1024) return {8, 1024, 2};
     return {8, 512, 4};
   }
   // 512 / 1024 channels, 1024-thread workgroups: few positions (depth 8 at batch 4: 512), so the segment narrows until
@@ -1156,8 +1155,7 @@ static LnvCfg lnv_cfg(int64_t C, int64_t B, int64_t L, bool bwd = false) {
   // forward C=512 L=1024 9.7 -> 8.0, L=512 6.9 -> 5.6, C=1024 7.4 -> 6.6 / 7.1 -> 6.3; backward 14.0 -> 12.9, 10.9 -> 9.9, 12.5 ->
   // 12.3, 9.3 -> 9.1: an 8-wave barrier and 8 partials per reduction instead of 16; 256 threads x 16 passes lose again).
   // ADP_LNV_NT / ADP_LNV_NT_BWD = 1024: the previous shape (A/B).
-  const char* e = getenv(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT");
-  if (!e || atoi(e) != 1024) {
+  if (adp_knob(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT", 512) != 1024) {
     const int lp = (C <= 512 && lpr == 1) ? 2 : lpr;
     return {lp, 512, C <= 512 ? lp : 2 * lp};
   }

@@ -501,7 +501,7 @@ int launch_wd(const adp_wgrad_desc& d, void* stream) {
 
 }  // namespace
 
-bool adp_wgrad_direct_eligible(const adp_wgrad_desc& d) {
+static bool adp_wgrad_direct_eligible(const adp_wgrad_desc& d) {
   if (d.dil != 1 || d.M * d.R > 256 || (d.prologue != 0 && d.prologue != 1)) return false;
   const bool s1 = d.stride == 1 && (d.KT == 1 || d.KT == 3) && d.pad == (d.KT - 1) / 2 &&
                   (d.up == 1 || d.up == 2 || d.up == 4);
@@ -514,13 +514,13 @@ bool adp_wgrad_direct_eligible(const adp_wgrad_desc& d) {
   return wd_plan(d).lds <= WD_LDS_BIG * sizeof(float);
 }
 
-int64_t adp_wgrad_direct_ws_floats(const adp_wgrad_desc& d) {
+static int64_t adp_wgrad_direct_ws_floats(const adp_wgrad_desc& d) {
   if (wd8_ok(d) && d.B <= 65535) return (int64_t)wd8_bpb(d) * d.B * (d.M * d.R * d.KT + d.M);
   if (wdu4_ok(d)) return (int64_t)wdu4_bpb(d) * d.B * (d.M * d.R * d.KT + d.M);
   return (int64_t)wd_plan(d).blocks * (d.M * d.R * d.KT + d.M);
 }
 
-int adp_wgrad_direct(const adp_wgrad_desc& d, void* stream) {
+static int adp_wgrad_direct(const adp_wgrad_desc& d, void* stream) {
   if (wd8_ok(d) && d.B <= 65535) return launch_wd8(d, stream);
   if (wdu4_ok(d)) return launch_wdu4(d, stream);
   if (d.stride == 2) return launch_wd<2, 2, 1>(d, stream);
@@ -533,4 +533,10 @@ int adp_wgrad_direct(const adp_wgrad_desc& d, void* stream) {
   if (d.up == 2) return launch_wd<1, 1, 2>(d, stream);
   if (d.up == 4) return launch_wd<1, 1, 4>(d, stream);
   return launch_wd<1, 1, 1>(d, stream);
+}
+
+const adp_wgrad_family& adp_wgrad_family_direct() {
+  static const adp_wgrad_family f = {"wgrad_direct", adp_wgrad_direct_eligible, adp_wgrad_direct,
+                                                    adp_wgrad_direct_ws_floats, nullptr, nullptr};
+  return f;
 }

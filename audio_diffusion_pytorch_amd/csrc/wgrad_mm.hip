@@ -702,8 +702,7 @@ WgPlan wg_plan(const adp_wgrad_desc& d, int n = 1, int64_t slots64 = 256) {  // 
   // (32 x 32 tiles WITHOUT the position split were measured for the 512-channel layers: batch 4 +0.13 ms, batch 1 -0.08 ms)
   int64_t ns = p.bm == 64 ? ns64 : ns32;
   if (n > 1) {
-    const char* e = getenv("ADP_WGRAD_BATCH_SPLIT");
-    if (!e || e[0] != '0') ns = p.bm == 64 ? wg_split(t64 * n, total, slots64) : wg_split(t32 * n, total, 768);
+    if (adp_knob_on("ADP_WGRAD_BATCH_SPLIT")) ns = p.bm == 64 ? wg_split(t64 * n, total, slots64) : wg_split(t32 * n, total, 768);
   }
   p.cps = adp_cdiv(total, ns);
   p.nsplit = adp_cdiv(total, p.cps);
@@ -789,7 +788,7 @@ __global__ __launch_bounds__(256) void adp_wgrad_reduce_small_kernel(adp_wgr_bat
 }
 
 // n <= ADP_WGR_BATCH weight gradients of ONE shape (nsplit, cnt, M; dbias all set or all NULL) in one launch
-int adp_wgrad_reduce_n(const float* const* ws, float* const* dw, float* const* dbias, int n, int64_t nsplit, int64_t cnt,
+static int adp_wgrad_reduce_n(const float* const* ws, float* const* dw, float* const* dbias, int n, int64_t nsplit, int64_t cnt,
                        int64_t M, int accumulate, void* stream) {
   adp_wgr_batch t;
   for (int i = 0; i < ADP_WGR_BATCH; ++i) {
@@ -811,6 +810,20 @@ int adp_wgrad_reduce_n(const float* const* ws, float* const* dw, float* const* d
 int adp_wgrad_reduce(const float* ws, int64_t nsplit, int64_t cnt, int64_t M, float* dw, float* dbias, int accumulate,
                      void* stream) {
   return adp_wgrad_reduce_n(&ws, &dw, dbias ? &dbias : nullptr, 1, nsplit, cnt, M, accumulate, stream);
+}
+
+extern "C" int adp_wgrad_reduce_batch(const float* const* ws, float* const* dw, float* const* dbias, int64_t n, int64_t nsplit,
+                                      int64_t cnt, int64_t M, int64_t accumulate, void* stream) {
+  if (!ws || !dw) return ADP_ERR_NULL;
+  if (n <= 0 || nsplit < 1 || cnt <= 0 || M <= 0) return ADP_ERR_SHAPE;
+  for (int64_t i = 0; i < n; ++i)
+    if (!ws[i] || !dw[i] || (dbias && !dbias[i])) return ADP_ERR_NULL;
+  for (int64_t i = 0; i < n; i += ADP_WGR_BATCH) {
+    const int k = (int)(n - i < ADP_WGR_BATCH ? n - i : ADP_WGR_BATCH);
+    const int rc = adp_wgrad_reduce_n(ws + i, dw + i, dbias ? dbias + i : nullptr, k, nsplit, cnt, M, (int)(accumulate & 1), stream);
+    if (rc != ADP_OK) return rc;
+  }
+  return ADP_OK;
 }
 
 namespace {
@@ -851,7 +864,7 @@ int pick_wg(const adp_wgrad_desc* ds, int n, void* stream) {
         // needs no more scratch than the lone launch's plan sized (adp_wgrad_mm_ws_floats).  ADP_WG_SOLO=0 / 1 forces either.
         const WgPlan ps = wg_plan(ds[0], n, 512);
         const int64_t t64 = (ds[0].M / 64) * (ds[0].R / 64);
-        const char* so = getenv("ADP_WG_SOLO");
+        const char* so = adp_knob_raw("ADP_WG_SOLO");
         const bool fits = ps.bm == 64 && (ps.nsplit == 1 || ps.nsplit <= wg_plan(ds[0]).nsplit);
         const bool solo = fits && (so ? so[0] == '1' : (t64 * n * ps.nsplit >= 512 && ps.cps >= 4));  // (batch 1, 4 chunks per block: step 6.16 -> 6.11 ms)
         if (solo) return launch_wg<64, KT, S, UP, PRO, true, true, 1, 1>(ds, n, ps, stream);
@@ -870,25 +883,20 @@ int pick_wg(const adp_wgrad_desc* ds, int n, void* stream) {
 // (ADP_CONV_WINO, conv_mm.hip), for layers with at least ADP_WINO_WGRAD_MIN_R (default 32) channels
 bool wg_winograd(const adp_wgrad_desc& d) {
   if (!adp_winograd_enabled()) return false;
-  const char* mr = getenv("ADP_WINO_WGRAD_MIN_R");
-  const int64_t min_r = mr ? atoll(mr) : 32;
-  return d.KT == 3 && d.stride == 1 && d.pad == 1 && d.R >= min_r;
+  return d.KT == 3 && d.stride == 1 && d.pad == 1 && d.R >= adp_knob("ADP_WINO_WGRAD_MIN_R", 32);
 }
 
 // F(4,3) form (W4) of the same: ADP_WGRAD_WINO4 (read per call; "0" = F(2,3)), layers with at least ADP_WINO4_WGRAD_MIN_R
 // (default 32) channels
 bool wg_winograd4(const adp_wgrad_desc& d) {
-  const char* e = getenv("ADP_WGRAD_WINO4");
-  if (e && e[0] == '0') return false;
-  const char* mr = getenv("ADP_WINO4_WGRAD_MIN_R");
-  const char* u = getenv("ADP_WGRAD_WINO4_UP");  // (A/B: "0" keeps the UpsampleItem convs' gradients on F(2,3))
-  if (d.up != 1 && u && u[0] == '0') return false;
-  return wg_winograd(d) && d.R >= (mr ? atoll(mr) : 32);  // (round 6: also the 32-channel layers -- 92 -> 85 us per batched launch)
+  if (!adp_knob_on("ADP_WGRAD_WINO4")) return false;
+  if (d.up != 1 && !adp_knob_on("ADP_WGRAD_WINO4_UP")) return false;  // (A/B: "0" keeps the UpsampleItem convs' gradients on F(2,3))
+  return wg_winograd(d) && d.R >= adp_knob("ADP_WINO4_WGRAD_MIN_R", 32);  // (round 6: also the 32-channel layers -- 92 -> 85 us per batched launch)
 }
 
 }  // namespace
 
-bool adp_wgrad_mm_eligible(const adp_wgrad_desc& d) {
+static bool adp_wgrad_mm_eligible(const adp_wgrad_desc& d) {
   if (d.R1 != d.R || d.dil != 1) return false;
   const bool plain = d.stride == 1 && d.up == 1 && ((d.KT == 3 && d.pad == 1) || (d.KT == 1 && d.pad == 0));
   const bool upc = d.stride == 1 && (d.up == 2 || d.up == 4) && d.KT == 3 && d.pad == 1 && d.prologue == 0;
@@ -904,15 +912,15 @@ bool adp_wgrad_mm_eligible(const adp_wgrad_desc& d) {
   return true;
 }
 
-int64_t adp_wgrad_mm_nsplit(const adp_wgrad_desc& d) { return wg_plan(d).nsplit; }
+static int64_t adp_wgrad_mm_nsplit(const adp_wgrad_desc& d) { return wg_plan(d).nsplit; }
 
-int64_t adp_wgrad_mm_ws_floats(const adp_wgrad_desc& d) {
+static int64_t adp_wgrad_mm_ws_floats(const adp_wgrad_desc& d) {
   const WgPlan p = wg_plan(d);
   return p.nsplit * (d.M * d.R * d.KT + d.M);
 }
 
 // n <= ADP_WGR_BATCH weight gradients of one shape (descriptors equal up to their pointers) in one launch
-int adp_wgrad_mm_n(const adp_wgrad_desc* ds, int n, void* stream) {
+static int adp_wgrad_mm_n(const adp_wgrad_desc* ds, int n, void* stream) {
   const adp_wgrad_desc& d = ds[0];
   if (d.stride == 2) return pick_wg<2, 2, 1, 0>(ds, n, stream);
   if (d.stride == 4) return pick_wg<4, 4, 1, 0>(ds, n, stream);
@@ -924,4 +932,10 @@ int adp_wgrad_mm_n(const adp_wgrad_desc* ds, int n, void* stream) {
   return d.prologue == 1 ? pick_wg<1, 1, 1, 1>(ds, n, stream) : pick_wg<1, 1, 1, 0>(ds, n, stream);
 }
 
-int adp_wgrad_mm(const adp_wgrad_desc& d, void* stream) { return adp_wgrad_mm_n(&d, 1, stream); }
+static int adp_wgrad_mm(const adp_wgrad_desc& d, void* stream) { return adp_wgrad_mm_n(&d, 1, stream); }
+
+const adp_wgrad_family& adp_wgrad_family_mm() {
+  static const adp_wgrad_family f = {"wgrad_mm", adp_wgrad_mm_eligible, adp_wgrad_mm, adp_wgrad_mm_ws_floats,
+                                                adp_wgrad_mm_nsplit, adp_wgrad_mm_n};
+  return f;
+}

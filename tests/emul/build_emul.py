@@ -2,6 +2,7 @@
 host-side SIMT emulator (adp_rt_emul.h) into tests/emul/libadp_emul.so, so CPU-only tests can
 exercise tiling / indexing / reduction logic of the HIP kernels through the same C-ABI.
 Never imported by the package; never a fallback for the product path."""
+import importlib.util
 import os
 import subprocess
 
@@ -9,13 +10,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(REPO_ROOT, "audio_diffusion_pytorch_amd", "csrc")
 LIB_PATH = os.path.join(HERE, "libadp_emul.so")
-SOURCES = ["conv1d.hip", "conv_mm.hip", "conv_mm_m64.hip", "conv_mm_m32.hip", "conv_tile.hip", "conv_tilek.hip", "conv_tilek1.hip", "conv_mm4.hip", "wgrad_mm.hip", "conv_direct.hip", "wgrad_direct.hip", "norm.hip", "elementwise.hip", "resample.hip", "linear.hip", "attention.hip", "ctx_bank.hip", "probe.hip"]
+# the product build's source and header lists, loaded by path (importing the package would ask for the product library)
+_spec = importlib.util.spec_from_file_location("adp_product_build", os.path.join(REPO_ROOT, "audio_diffusion_pytorch_amd", "build.py"))
+product = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(product)
 
 
 def build(force: bool = False) -> str:
-    srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    deps = srcs + [os.path.join(CSRC, "adp_rt.h"), os.path.join(CSRC, "conv_internal.h"), os.path.join(CSRC, "conv_mm_impl.h"), os.path.join(HERE, "adp_rt_emul.h"),
-                   os.path.join(REPO_ROOT, "include", "adp.h")]
+    srcs = product.sources()
+    deps = srcs + product.headers() + [os.path.join(HERE, "adp_rt_emul.h")]
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
         return LIB_PATH
     objs, procs = [], []
