@@ -135,11 +135,21 @@ AR_SIGNATURES = {
     "adp_arv_plane": (c_int, [P, I, I, I, P, P]),
 }
 
+# the extension header include/adp_lt.h (learned-transform front end), one to one
+LT_SIGNATURES = {
+    "adp_lt_conv_out_len": (I, [I, I, I, I]),
+    "adp_lt_convt_out_len": (I, [I, I, I, I]),
+    "adp_lt_conv": (c_int, [P, P, I, I, I, I, I, I, I, I, P, P]),
+    "adp_lt_convt": (c_int, [P, P, I, I, I, I, I, I, I, I, I, P, P]),
+    "adp_lt_wgrad_ws_bytes": (I, [I, I, I, I, I]),
+    "adp_lt_wgrad": (c_int, [P, P, I, I, I, I, I, I, I, I, I, P, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h declare
+    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -40,8 +40,9 @@ DiffusionAR = _out_of_scope("DiffusionAR", "the native autoregressive path (Diff
 
 def LTPlugin(*args, **kwargs):
     """Reference: a factory (components.py:113-159), so a plain callable here too."""
-    raise NotImplementedError("LTPlugin is not part of the MI355X-native hot path (learned-transform front end, not on "
-                              "the UNetV0 denoising path); see DESIGN.md section 7")
+    raise NotImplementedError("LTPlugin is not part of the MI355X-native hot path (the native learned-transform front end is "
+                              "audio_diffusion_pytorch_amd.lt.LTPlugin; this top-level name is still the stub); see "
+                              "DESIGN.md section 7")
 
 
 __all__ = [

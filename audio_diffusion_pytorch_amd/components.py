@@ -6,7 +6,7 @@ kernel-backed module (unet.UNetV0Net); use_embedding_cfg wraps it in the classif
 (the guided and the masked evaluation run as ONE batched U-Net call); use_text_conditioning wraps it in the
 text-conditioning module (the embedder is the caller's module; the t5-base default needs local weights);
 use_modulation=False selects SkipCat; use_time_conditioning=False leaves `features` to the caller.  Out of scope
-(SURVEY.md section 2): LTPlugin, MelSpectrogram.
+(SURVEY.md section 2): MelSpectrogram here (vocoder.py has it); LTPlugin lives in lt.py.
 """
 from typing import Callable, Optional, Sequence
 
@@ -204,17 +204,40 @@ def load_reference_state_dict(net: nn.Module, sd) -> dict:
     fixed-embedding table (identified by its `[embedding_max_length, embedding_features]` shape right in front of the
     blocks) into ClassifierFreeGuidanceNet.fixed_embedding, and the frozen pretrained T5 tensors are NOT loaded (they are
     t5-base's own weights; the embedder here is the caller's module or the local t5-base).  Returns {checkpoint key: what it
-    was loaded as / "skipped: ..."}."""
-    cfg_net, has_text, inner = None, False, net
+    was loaded as / "skipped: ..."}.
+    Around an `lt.LTPlugin` module (UNVERIFIED offline as well) the reference registers [encode.weight, decode.weight, net
+    tensors...]: the two tensors in front are shape-checked and copied, the rest goes down the path above."""
+    from .lt import LTNet
+    cfg_net, has_text, inner, lt_net = None, False, net, None
     while not isinstance(inner, UNetV0Net):
         if isinstance(inner, ClassifierFreeGuidanceNet):
             cfg_net = inner
         elif isinstance(inner, TextConditioningNet):
             has_text = True
+        elif isinstance(inner, LTNet):
+            if lt_net is not None or cfg_net is not None or has_text:
+                raise TypeError("load_reference_state_dict: an LTPlugin module is accepted around the whole UNetV0(...) only "
+                                "(the reference registers its two tensors in front of the net's); found it "
+                                + ("nested in another LTPlugin module" if lt_net is not None else
+                                   "inside a classifier-free-guidance / text-conditioning wrapper"))
+            lt_net = inner
         elif not isinstance(inner, _AppendChannelsNet):
             raise TypeError(f"load_reference_state_dict: {type(inner).__name__} does not wrap a UNetV0")
         inner = inner.net
     theirs = [(k, v) for k, v in sd.items() if torch.is_tensor(v) and v.dtype.is_floating_point]
+    lt_loaded = {}
+    if lt_net is not None:
+        if len(theirs) < 2:
+            raise ValueError("checkpoint of an LTPlugin net must start with encode.weight and decode.weight")
+        for (k, v), (name, mod) in zip(theirs[:2], (("encode.weight", lt_net.encode), ("decode.weight", lt_net.decode))):
+            if tuple(v.shape) != tuple(mod.weight.shape):
+                raise ValueError(f"checkpoint entry {k!r} has shape {tuple(v.shape)} where the learned transform's {name} "
+                                 f"{tuple(mod.weight.shape)} is expected (the plugin's two tensors come first)")
+        with torch.no_grad():
+            lt_net.encode.weight.copy_(theirs[0][1])
+            lt_net.decode.weight.copy_(theirs[1][1])
+        lt_loaded = {theirs[0][0]: "encode.weight", theirs[1][0]: "decode.weight"}
+        theirs = theirs[2:]
     n_unet = len(inner.a_unet_key_order())
     n_time = sum(1 for k in inner.a_unet_key_order() if k.startswith("time_"))
     n_extra = len(theirs) - n_unet
@@ -223,7 +246,7 @@ def load_reference_state_dict(net: nn.Module, sd) -> dict:
                          + (" + the fixed-embedding table" if cfg_net is not None else "")
                          + (" + the text encoder's" if has_text else ""))
     extras = theirs[n_time:n_time + n_extra]
-    out = {}
+    out = dict(lt_loaded)
     if cfg_net is not None:
         k, v = extras[-1]
         if tuple(v.shape) != tuple(cfg_net.fixed_embedding.weight.shape):

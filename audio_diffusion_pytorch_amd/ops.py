@@ -767,6 +767,58 @@ def tflat_wgrad(spec: Tensor, g: Tensor, K: int, hop: int, dw: Optional[Tensor] 
     return dw
 
 
+# ---- learned-transform front end (include/adp_lt.h)
+LT_ZERO, LT_REFLECT = 0, 1   # lt_conv / lt_wgrad: how the signal continues past its ends
+LT_PLAIN, LT_FOLD = 0, 1     # lt_convt: outside positions dropped / added to their mirror positions
+
+
+def _lt_out(shape, like: Tensor) -> Tensor:
+    out = torch.empty(shape, dtype=torch.float32, device=like.device)
+    if os.environ.get("ADP_DEBUG_POISON", "0") == "1":  # (test-suite: an element nobody wrote cannot pass)
+        out.fill_(float("nan"))
+    return out
+
+
+def lt_conv(x: Tensor, w: Tensor, stride: int, pad: int, mode: int) -> Tensor:
+    """x [B, C, T], w [O, C, K] -> [B, O, L]: the strided convolution over the reflect- / zero-continued x (adp_lt_conv)."""
+    B, C, T = x.shape
+    O, K = w.shape[0], w.shape[2]
+    assert w.shape[1] == C, "lt_conv: weight is [out, in, kernel_size]"
+    y = _lt_out((B, O, _C.query("adp_lt_conv_out_len", T, K, stride, pad)), x)
+    _C.tag(flops=2 * y.numel() * C * K, shape=f"B{B} C{C} T{T} O{O} K{K} s{stride} p{pad} m{mode}")
+    _C.call("adp_lt_conv", ptr(x), ptr(w), B, C, T, O, K, stride, pad, mode, ptr(y), _C.stream())
+    return y
+
+
+def lt_convt(x: Tensor, w: Tensor, stride: int, pad: int, mode: int, T: Optional[int] = None) -> Tensor:
+    """x [B, C, L], w [C, O, K] -> [B, O, T]: the strided transposed convolution (adp_lt_convt).  LT_PLAIN: T is the
+    layer's own length; LT_FOLD: T is the length of the signal lt_conv(..., LT_REFLECT) read, whose adjoint this is."""
+    B, C, L = x.shape
+    O, K = w.shape[1], w.shape[2]
+    assert w.shape[0] == C, "lt_convt: weight is [in, out, kernel_size]"
+    if T is None:
+        assert mode == LT_PLAIN, "lt_convt: LT_FOLD needs the signal length T"
+        T = _C.query("adp_lt_convt_out_len", L, K, stride, pad)
+    out = _lt_out((B, O, T), x)
+    _C.tag(flops=2 * out.numel() * C * ((K + stride - 1) // stride), shape=f"B{B} C{C} L{L} O{O} K{K} s{stride} p{pad} m{mode}")
+    _C.call("adp_lt_convt", ptr(x), ptr(w), B, C, L, O, K, stride, pad, mode, T, ptr(out), _C.stream())
+    return out
+
+
+def lt_wgrad(u: Tensor, v: Tensor, K: int, stride: int, pad: int, mode: int, dw: Optional[Tensor] = None) -> Tensor:
+    """dw [A, Bc, K] = sum over (batch, frame) of u [B, A, L] times the continued v [B, Bc, T] at l stride + k - pad;
+    written, not accumulated, bit-identical from call to call (adp_lt_wgrad)."""
+    B, A, L = u.shape
+    Bc, T = v.shape[1], v.shape[2]
+    assert v.shape[0] == B, "lt_wgrad: batch mismatch"
+    if dw is None:
+        dw = _lt_out((A, Bc, K), u)
+    ws = _ws(_C.query("adp_lt_wgrad_ws_bytes", B, A, Bc, L, K), u)
+    _C.tag(flops=2 * B * L * A * Bc * K, shape=f"B{B} A{A} Bc{Bc} L{L} K{K} s{stride} p{pad} m{mode}")
+    _C.call("adp_lt_wgrad", ptr(u), ptr(v), B, A, Bc, L, T, K, stride, pad, mode, ptr(dw), ptr(ws), _C.stream())
+    return dw
+
+
 def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(a)
