@@ -145,11 +145,22 @@ LT_SIGNATURES = {
     "adp_lt_wgrad": (c_int, [P, P, I, I, I, I, I, I, I, I, I, P, P, P]),
 }
 
+# the extension header include/adp_enc.h (mel encoder: overlapping strided downsample, tanh bottleneck), one to one
+ENC_SIGNATURES = {
+    "adp_enc_down_out_len": (I, [I, I]),
+    "adp_enc_down_fwd": (c_int, [P, P, P, I, I, I, I, I, P, P]),
+    "adp_enc_down_dgrad": (c_int, [P, P, I, I, I, I, I, P, P]),
+    "adp_enc_down_wgrad_ws_bytes": (I, [I, I, I, I, I]),
+    "adp_enc_down_wgrad": (c_int, [P, P, I, I, I, I, I, P, P, P, P]),
+    "adp_enc_tanh_fwd": (c_int, [P, I, P, P]),
+    "adp_enc_tanh_bwd": (c_int, [P, P, I, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h declare
+    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

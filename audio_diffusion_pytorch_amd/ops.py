@@ -819,6 +819,84 @@ def lt_wgrad(u: Tensor, v: Tensor, K: int, stride: int, pad: int, mode: int, dw:
     return dw
 
 
+# ---- mel encoder (include/adp_enc.h)
+def _enc_call(name: str, label: str, nbytes: int, args, keep) -> None:
+    """One adp_enc_* launch; with _C.REPLAY set, the relaunch callable is recorded as ops.conv1d records its convs."""
+    _C.call(name, *args, _C.stream())
+    if _C.REPLAY is not None:
+        _C.REPLAY.append((label, nbytes, lambda args=args, keep=keep: _C.call(name, *args, _C.stream())))
+
+
+def enc_down_out_len(L: int, f: int) -> int:
+    return _C.query("adp_enc_down_out_len", L, f)
+
+
+def enc_down_fwd(x: Tensor, w: Tensor, bias: Tensor, f: int) -> Tensor:
+    """x [B, R, L], w [M, R, 2f+1], bias [M] -> [B, M, ceil(L / f)]: Conv1d(kernel 2f+1, stride f, padding f)
+    (adp_enc_down_fwd)."""
+    B, R, L = x.shape
+    M = w.shape[0]
+    assert w.shape[1] == R and w.shape[2] == 2 * f + 1 and bias.shape == (M,), "enc_down_fwd: weight is [out, in, 2f+1]"
+    y = _lt_out((B, M, enc_down_out_len(L, f)), x)
+    label = f"B{B} R{R} M{M} L{L} f{f}"
+    nbytes = 4 * (x.numel() + y.numel() + w.numel())
+    _C.tag(flops=2 * y.numel() * R * (2 * f + 1), bytes=nbytes, shape=label)
+    _enc_call("adp_enc_down_fwd", "enc_down_fwd " + label, nbytes, (ptr(x), ptr(w), ptr(bias), B, R, M, L, f, ptr(y)),
+              (x, w, bias, y))
+    return y
+
+
+def enc_down_dgrad(dy: Tensor, w: Tensor, f: int, L: int) -> Tensor:
+    """dy [B, M, ceil(L / f)], w [M, R, 2f+1] -> dx [B, R, L], the data gradient of enc_down_fwd (adp_enc_down_dgrad)."""
+    B, M, N = dy.shape
+    R = w.shape[1]
+    assert w.shape[0] == M and w.shape[2] == 2 * f + 1, "enc_down_dgrad: weight is [out, in, 2f+1]"
+    assert N == enc_down_out_len(L, f), "enc_down_dgrad: the output gradient is not the layer's output length"
+    dx = _lt_out((B, R, L), dy)
+    label = f"B{B} R{R} M{M} L{L} f{f}"
+    nbytes = 4 * (dy.numel() + dx.numel() + w.numel())
+    _C.tag(flops=2 * dy.numel() * R * (2 * f + 1), bytes=nbytes, shape=label)
+    _enc_call("adp_enc_down_dgrad", "enc_down_dgrad " + label, nbytes, (ptr(dy), ptr(w), B, R, M, L, f, ptr(dx)), (dy, w, dx))
+    return dx
+
+
+def enc_down_wgrad(x: Tensor, dy: Tensor, f: int, dw: Optional[Tensor] = None, dbias: Optional[Tensor] = None):
+    """(dw [M, R, 2f+1], dbias [M]) of enc_down_fwd for the input x [B, R, L] and the output gradient dy [B, M, ceil(L / f)];
+    written, not accumulated, bit-identical from call to call (adp_enc_down_wgrad)."""
+    B, R, L = x.shape
+    M, N = dy.shape[1], dy.shape[2]
+    assert dy.shape[0] == B and N == enc_down_out_len(L, f), "enc_down_wgrad: output gradient shape mismatch"
+    if dw is None:
+        dw = _lt_out((M, R, 2 * f + 1), x)
+    if dbias is None:
+        dbias = _lt_out((M,), x)
+    ws = _ws(_C.query("adp_enc_down_wgrad_ws_bytes", B, R, M, L, f), x)
+    label = f"B{B} R{R} M{M} L{L} f{f}"
+    nbytes = 4 * (x.numel() + dy.numel() + dw.numel())
+    _C.tag(flops=2 * dy.numel() * R * (2 * f + 1), bytes=nbytes, shape=label)
+    _enc_call("adp_enc_down_wgrad", "enc_down_wgrad " + label, nbytes,
+              (ptr(x), ptr(dy), B, R, M, L, f, ptr(dw), ptr(dbias), ptr(ws)), (x, dy, dw, dbias, ws))
+    return dw, dbias
+
+
+def enc_tanh_fwd(h: Tensor) -> Tensor:
+    """tanh(h) (adp_enc_tanh_fwd)."""
+    z = _lt_out(h.shape, h)
+    _C.tag(bytes=8 * h.numel(), shape=f"n{h.numel()}")
+    _enc_call("adp_enc_tanh_fwd", f"enc_tanh_fwd n{h.numel()}", 8 * h.numel(), (ptr(h), h.numel(), ptr(z)), (h, z))
+    return z
+
+
+def enc_tanh_bwd(z: Tensor, dz: Tensor) -> Tensor:
+    """dz (1 - z^2) for z = tanh(h) (adp_enc_tanh_bwd)."""
+    assert dz.shape == z.shape, "enc_tanh_bwd: gradient shape mismatch"
+    dh = _lt_out(z.shape, z)
+    _C.tag(bytes=12 * z.numel(), shape=f"n{z.numel()}")
+    _enc_call("adp_enc_tanh_bwd", f"enc_tanh_bwd n{z.numel()}", 12 * z.numel(), (ptr(z), ptr(dz), z.numel(), ptr(dh)),
+              (z, dz, dh))
+    return dh
+
+
 def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(a)
