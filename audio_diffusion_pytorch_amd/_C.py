@@ -156,11 +156,20 @@ ENC_SIGNATURES = {
     "adp_enc_tanh_bwd": (c_int, [P, P, I, P, P]),
 }
 
+# the extension header include/adp_t5.h (frozen T5 text encoder: embedding, RMS norm, token GEMM, attention), one to one
+T5_SIGNATURES = {
+    "adp_t5_embed": (c_int, [P, P, I, I, I, P, P]),
+    "adp_t5_rmsnorm": (c_int, [P, P, I, I, F, P, P]),
+    "adp_t5_linear_ws_bytes": (I, [I, I, I]),
+    "adp_t5_linear": (c_int, [P, P, P, I, I, I, I, P, P, P]),
+    "adp_t5_attn": (c_int, [P, P, P, P, I, I, I, I, I, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h declare
+    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

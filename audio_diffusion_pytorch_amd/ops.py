@@ -897,6 +897,69 @@ def enc_tanh_bwd(z: Tensor, dz: Tensor) -> Tensor:
     return dh
 
 
+# ---- frozen T5 text encoder (include/adp_t5.h); forward only
+def t5_embed(ids: Tensor, table: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """ids int64 [T], table [V, d] -> [T, d]; an id outside [0, V) gives a row of zeros (adp_t5_embed)."""
+    T, (V, d) = ids.numel(), table.shape
+    if out is None:
+        out = _lt_out((T, d), table)
+    _C.tag(bytes=8 * T * d, shape=f"T{T} V{V} d{d}")
+    _C.call("adp_t5_embed", ptr(ids, torch.int64), ptr(table), T, V, d, ptr(out), _C.stream())
+    return out
+
+
+def t5_rmsnorm(x: Tensor, g: Tensor, eps: float, out: Optional[Tensor] = None) -> Tensor:
+    """x [T, d] * rsqrt(mean x^2 + eps) * g [d]: T5's LayerNorm (adp_t5_rmsnorm)."""
+    T, d = x.shape
+    assert g.shape == (d,), "t5_rmsnorm: the weight is [d]"
+    if out is None:
+        out = _lt_out((T, d), x)
+    _C.tag(bytes=8 * T * d, shape=f"T{T} d{d}")
+    _C.call("adp_t5_rmsnorm", ptr(x), ptr(g), T, d, float(eps), ptr(out), _C.stream())
+    return out
+
+
+def t5_linear_ws_bytes(T: int, K: int, N: int) -> int:
+    return _C.query("adp_t5_linear_ws_bytes", T, K, N)
+
+
+def t5_linear(x: Tensor, w: Tensor, res: Optional[Tensor] = None, relu: bool = False, out: Optional[Tensor] = None,
+              ws: Optional[Tensor] = None) -> Tensor:
+    """res + act(x [T, K] @ w [N, K]^T) -> [T, N]; `out` may be `res` itself (adp_t5_linear).  `ws`: at least
+    t5_linear_ws_bytes(T, K, N) bytes, allocated here when not given."""
+    T, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K, "t5_linear: the weight is [out, in]"
+    assert res is None or res.shape == (T, N), "t5_linear: the residual is [T, out]"
+    if out is None:
+        out = _lt_out((T, N), x)
+    nbytes = t5_linear_ws_bytes(T, K, N)
+    if ws is None and nbytes:
+        ws = _ws(nbytes, x)
+    assert nbytes == 0 or ws.numel() * 4 >= nbytes, "t5_linear: workspace too small"
+    _C.tag(flops=2 * T * K * N, bytes=4 * (T * K + N * K + T * N), shape=f"T{T} K{K} N{N}")
+    _C.call("adp_t5_linear", ptr(x), ptr(w), ptr(res), T, K, N, int(bool(relu)), ptr(out), ptr(ws) if nbytes else None,
+            _C.stream())
+    return out
+
+
+def t5_attn(qkv: Tensor, rel_table: Tensor, bucket: Tensor, mask_u8: Optional[Tensor], heads: int,
+            out: Optional[Tensor] = None) -> Tensor:
+    """qkv [B, m, 3 H dk], rel_table [nb, H], bucket int32 [2m - 1], mask uint8 [B, m] or None -> [B, m, H dk]: T5
+    self-attention with the relative-position bias and the key mask (adp_t5_attn)."""
+    B, m, W = qkv.shape
+    assert W % (3 * heads) == 0, "t5_attn: the packed projection is [B, m, 3 H dk]"
+    dk, nb = W // (3 * heads), rel_table.shape[0]
+    assert rel_table.shape == (nb, heads) and bucket.shape == (2 * m - 1,), "t5_attn: bias table [nb, H], bucket [2m - 1]"
+    assert mask_u8 is None or mask_u8.shape == (B, m), "t5_attn: the mask is [B, m]"
+    if out is None:
+        out = _lt_out((B, m, heads * dk), qkv)
+    _C.tag(flops=4 * B * heads * m * m * dk, bytes=4 * (qkv.numel() + out.numel()), shape=f"B{B} H{heads} dk{dk} m{m}")
+    _C.call("adp_t5_attn", ptr(qkv), ptr(rel_table), ptr(bucket, torch.int32), ptr(mask_u8, torch.uint8), B, heads, dk, m, nb,
+            ptr(out), _C.stream())
+    return out
+
+
 def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(a)
