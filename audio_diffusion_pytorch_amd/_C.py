@@ -165,11 +165,20 @@ T5_SIGNATURES = {
     "adp_t5_attn": (c_int, [P, P, P, P, I, I, I, I, I, P, P]),
 }
 
+# the extension header include/adp_rng.h (Philox4x32-10 normals from a device (seed, draw) row; the inpainting step that
+# draws from it), one to one
+RNG_SIGNATURES = {
+    "adp_philox_bits": (c_int, [P, I, P, P]),
+    "adp_randn": (c_int, [P, I, P, P]),
+    "adp_v_inpaint_step_rng": (c_int, [P, P, P, P, P, P, I, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h declare
+    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
+                              **RNG_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

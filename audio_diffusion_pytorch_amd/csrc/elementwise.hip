@@ -11,6 +11,7 @@
 #endif
 #include "adp.h"
 #include "adp_ar.h"
+#include "inpaint_blend.h"
 
 namespace {
 
@@ -149,19 +150,13 @@ __global__ __launch_bounds__(256) void v_step2_kernel(const float* x, const floa
 }
 
 // one VInpainter resample step (diffusion.py:339-350): rotate (x, v) from noise level i to level j, re-noise the
-// source to level j with the caller's draw, keep the source where mask is set
+// source to level j with the caller's draw, keep the source where mask is set (the arithmetic: inpaint_blend.h)
 __global__ __launch_bounds__(256) void v_inpaint_kernel(const float* x, const float* v, const float* src,
                                                         const float* noise, const uint8_t* mask, const float* ab4,
                                                         int64_t n, float* xo) {
-  const float a0 = ab4[0], b0 = ab4[1], a1 = ab4[2], b1 = ab4[3];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float xv = x[i], vv = v[i];
-    const float x_pred = a0 * xv - b0 * vv;
-    const float n_pred = b0 * xv + a0 * vv;
-    const float xn = a1 * x_pred + b1 * n_pred;
-    const float sn = a1 * src[i] + b1 * noise[i];
-    xo[i] = mask[i] ? sn : xn;
-  }
+  const VInpaintCoef c{ab4[0], ab4[1], ab4[2], ab4[3]};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    xo[i] = adp_v_inpaint_blend(c, x[i], v[i], src[i], noise[i], mask[i] != 0);
 }
 
 // classifier-free guidance mix of the two halves of a batched [2B, ...] evaluation:

@@ -1,0 +1,199 @@
+// Counter-based normal generator (Philox4x32-10 + Box-Muller) and the VInpainter resample step that draws from it
+// (include/adp_rng.h).  Seed and draw index are read from a 4-word DEVICE row, so one captured launch serves every draw:
+// the host copies the next row in front of the replay.
+//   adp_philox_bits        : the raw words of a row's stream (the integer generator, tested exactly)
+//   adp_randn              : the normals of a row's stream, 1 write
+//   adp_v_inpaint_step_rng : adp_v_inpaint_step with the noise formed in registers, 3 reads + 1 byte, 1 write
+// One thread owns one group of four elements per pass: one Philox call (ten rounds of two 32x32->64 multiplies) and two
+// Box-Muller pairs.  No LDS, no atomics, no cross-lane traffic; ordinary vector or single-element stores only.
+#include "adp_rt.h"
+#include "adp.h"
+#include "adp_rng.h"
+#include "inpaint_blend.h"
+
+namespace {
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+struct alignas(16) U32x4 {
+  uint32_t w[4];
+};
+
+struct RngRow {
+  uint32_t seed_lo, seed_hi, draw;
+};
+
+__device__ __forceinline__ RngRow rng_row(const uint32_t* rng4) { return RngRow{rng4[0], rng4[1], rng4[2]}; }
+
+// Philox4x32-10 on counter (lo32(g), hi32(g), draw, 0) under key (seed_lo, seed_hi): words 4g .. 4g+3 of the row's stream
+__device__ __forceinline__ U32x4 rng_words(const RngRow& r, int64_t g) {
+  uint32_t c0 = (uint32_t)((uint64_t)g & 0xFFFFFFFFu), c1 = (uint32_t)((uint64_t)g >> 32), c2 = r.draw, c3 = 0u;
+  uint32_t k0 = r.seed_lo, k1 = r.seed_hi;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += PHILOX_W0;
+    k1 += PHILOX_W1;
+  }
+  return U32x4{{c0, c1, c2, c3}};
+}
+
+// Box-Muller on one pair of words: u = ((r >> 8) + 0.5) 2^-24 for both; (sqrt(-2 ln u_a) cos(2 pi u_b), ... sin(2 pi u_b)).
+// u_a = m 2^-25 with m = 2 (ra >> 8) + 1 a 25-bit odd integer: h is the float nearest to m, d = m - h in {-1, 0, 1} (exact in
+// integers), ln u_a = logf(h 2^-25) + d / h up to (d / h)^2 / 2 < 2^-49.  Without the d term the radius would be off by up
+// to 1e-4 where u_a is within 2^-16 of 1.
+__device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& z_cos, float& z_sin) {
+  const uint32_t m = 2u * (ra >> 8) + 1u;
+  const float h = (float)m;
+  const int d = (int)m - (int)(uint32_t)h;
+  const float ln_u = logf(h * 0x1p-25f) + (float)d / h;
+  const float radius = sqrtf(-2.0f * ln_u);
+  const float ub = ((float)(rb >> 8) + 0.5f) * 0x1p-24f;
+  float s, c;
+  sincosf(6.28318530717958647692f * ub, &s, &c);
+  z_cos = radius * c;
+  z_sin = radius * s;
+}
+
+// the draw: normals 4g .. 4g+3 of the row's stream
+__device__ __forceinline__ f32x4 rng_normal4(const RngRow& r, int64_t g) {
+  const U32x4 w = rng_words(r, g);
+  float z0, z1, z2, z3;
+  box_muller(w.w[0], w.w[1], z0, z1);
+  box_muller(w.w[2], w.w[3], z2, z3);
+  const f32x4 z = {z0, z1, z2, z3};
+  return z;
+}
+
+__device__ __forceinline__ int64_t rng_groups(int64_t n) { return n / 4 + (n % 4 != 0); }
+
+// VEC: out is 16-byte aligned -> whole groups leave as one 16-byte store; the tail group and the unaligned case as single
+// predicated stores
+template <bool VEC>
+__global__ __launch_bounds__(256) void philox_bits_kernel(const uint32_t* rng4, int64_t n, uint32_t* out) {
+  const RngRow r = rng_row(rng4);
+  const int64_t groups = rng_groups(n);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const U32x4 w = rng_words(r, g);
+    const int64_t e = 4 * g;
+    if (VEC && e + 4 <= n) {
+      *(U32x4*)(out + e) = w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < n) out[e + k] = w.w[k];
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void randn_kernel(const uint32_t* rng4, int64_t n, float* out) {
+  const RngRow r = rng_row(rng4);
+  const int64_t groups = rng_groups(n);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const f32x4 z = rng_normal4(r, g);
+    const int64_t e = 4 * g;
+    if (VEC && e + 4 <= n) {
+      *(f32x4*)(out + e) = z;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < n) out[e + k] = z[k];
+    }
+  }
+}
+
+// VEC: x, v, src and xo are 16-byte aligned and mask is 4-byte aligned.  A group none of whose elements keeps the source
+// needs no noise and skips the draw (the values of the others do not depend on it).
+template <bool VEC>
+__global__ __launch_bounds__(256) void v_inpaint_rng_kernel(const float* x, const float* v, const float* src,
+                                                            const uint8_t* mask, const float* ab4, const uint32_t* rng4,
+                                                            int64_t n, float* xo) {
+  const VInpaintCoef c{ab4[0], ab4[1], ab4[2], ab4[3]};
+  const RngRow r = rng_row(rng4);
+  const int64_t groups = rng_groups(n);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t e = 4 * g;
+    f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (VEC && e + 4 <= n) {
+      const f32x4 xv = *(const f32x4*)(x + e), vv = *(const f32x4*)(v + e), sv = *(const f32x4*)(src + e);
+      const uint32_t m4 = *(const uint32_t*)(mask + e);
+      if (m4 != 0u) z = rng_normal4(r, g);
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        o[k] = adp_v_inpaint_blend(c, xv[k], vv[k], sv[k], z[k], ((m4 >> (8 * k)) & 0xFFu) != 0u);
+      *(f32x4*)(xo + e) = o;
+    } else {
+      bool keep[4], any = false;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        keep[k] = e + k < n && mask[e + k] != 0;
+        any = any || keep[k];
+      }
+      if (any) z = rng_normal4(r, g);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < n) xo[e + k] = adp_v_inpaint_blend(c, x[e + k], v[e + k], src[e + k], z[k], keep[k]);
+    }
+  }
+}
+
+// one group per thread and pass
+unsigned rng_grid(int64_t n) {
+  int64_t g = adp_cdiv(adp_cdiv(n, 4), 256);
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
+
+}  // namespace
+
+extern "C" int adp_philox_bits(const uint32_t* rng4, int64_t n_words, uint32_t* out, void* stream) {
+  if (!rng4 || !out) return ADP_ERR_NULL;
+  if (n_words < 0) return ADP_ERR_SHAPE;
+  if (misaligned(rng4, 4) || misaligned(out, 4)) return ADP_ERR_ALIGN;
+  if (n_words == 0) return ADP_OK;
+  if (!misaligned(out, 16))
+    ADP_LAUNCH(philox_bits_kernel<true>, dim3(rng_grid(n_words)), dim3(256), stream, rng4, n_words, out);
+  else
+    ADP_LAUNCH(philox_bits_kernel<false>, dim3(rng_grid(n_words)), dim3(256), stream, rng4, n_words, out);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_randn(const uint32_t* rng4, int64_t n, float* out, void* stream) {
+  if (!rng4 || !out) return ADP_ERR_NULL;
+  if (n < 0) return ADP_ERR_SHAPE;
+  if (misaligned(rng4, 4) || misaligned(out, 4)) return ADP_ERR_ALIGN;
+  if (n == 0) return ADP_OK;
+  if (!misaligned(out, 16))
+    ADP_LAUNCH(randn_kernel<true>, dim3(rng_grid(n)), dim3(256), stream, rng4, n, out);
+  else
+    ADP_LAUNCH(randn_kernel<false>, dim3(rng_grid(n)), dim3(256), stream, rng4, n, out);
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_v_inpaint_step_rng(const float* x, const float* v, const float* source, const uint8_t* mask,
+                                      const float* ab4, const uint32_t* rng4, int64_t n, float* x_out, void* stream) {
+  if (!x || !v || !source || !mask || !ab4 || !rng4 || !x_out) return ADP_ERR_NULL;
+  if (n < 0) return ADP_ERR_SHAPE;
+  if (misaligned(x, 4) || misaligned(v, 4) || misaligned(source, 4) || misaligned(ab4, 4) || misaligned(rng4, 4) ||
+      misaligned(x_out, 4))
+    return ADP_ERR_ALIGN;
+  if (n == 0) return ADP_OK;
+  const bool vec = !misaligned(x, 16) && !misaligned(v, 16) && !misaligned(source, 16) && !misaligned(x_out, 16) &&
+                   !misaligned(mask, 4);
+  if (vec)
+    ADP_LAUNCH(v_inpaint_rng_kernel<true>, dim3(rng_grid(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
+  else
+    ADP_LAUNCH(v_inpaint_rng_kernel<false>, dim3(rng_grid(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
+  return ADP_LAUNCH_OK();
+}

@@ -208,16 +208,14 @@ def _kw_rebuild(value, it):
     return value
 
 
-class VSampler(Sampler):
+class _CapturedSteps:
+    """The cache of captured steps that `VSampler` and `VInpainter` share (mixed into an nn.Module with a `net`): one step =
+    U-Net forward + update kernel in place on a static x, captured once per call STRUCTURE and replayed.  An entry is a tuple
+    whose layout belongs to the class that builds it, except that entry[6] is the parameter signature it was captured under."""
 
-    diffusion_types = [VDiffusion]
     GRAPH_CACHE_ENTRIES = 4  # captured steps kept (LRU); each owns its private activation pool
 
-    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), use_graph: bool = True):
-        super().__init__()
-        self.net = net
-        self.schedule = schedule
-        self.use_graph = use_graph
+    def _init_graph_cache(self):
         self._graph_cache: "OrderedDict" = OrderedDict()
         self.graph_captures = 0  # (visible to tests: steps captured / sampling runs served by replays)
         self.graph_replays = 0
@@ -228,6 +226,68 @@ class VSampler(Sampler):
         state = super().__getstate__()
         state.update(_graph_cache=OrderedDict(), graph_captures=0, graph_replays=0)
         return state
+
+    def _graph_lookup(self, x: Tensor, kwargs, extra_key=()):
+        """None (eager fallback) for kwargs that cannot be made static, else (key, names, live, psig, entry): the cache key
+        (x shape, device, kwarg names, tensor shapes / dtypes, python scalar values, `extra_key`), the sorted kwarg names, the
+        caller's kwarg tensors in traversal order, the net's parameter signature now, and the cached entry or None.  An
+        entry whose parameters moved or were replaced is dropped here (the graph holds their addresses): never replayed."""
+        from .graphed import param_signature, tracked_parameters
+        names = sorted(kwargs)
+        live: List[Tensor] = []
+        specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
+        if any(sp is None for _, sp in specs) or any(not t.is_cuda for t in live):
+            return None
+        key = (tuple(x.shape), x.device, specs) + tuple(extra_key)
+        psig = param_signature(tracked_parameters(self.net))
+        entry = self._graph_cache.get(key)
+        if entry is not None and entry[6] != psig:
+            del self._graph_cache[key]
+            entry = None
+        if entry is not None:
+            self._graph_cache.move_to_end(key)
+        return key, names, live, psig, entry
+
+    @staticmethod
+    def _static_kwargs(kwargs, names, live):
+        """Static copies of the kwarg tensors (filled with the caller's values) and the kwargs rebuilt around them."""
+        statics = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in live]
+        for st, t in zip(statics, live):
+            st.copy_(t)
+        it = iter(statics)
+        return statics, {k: _kw_rebuild(kwargs[k], it) for k in names}
+
+    @staticmethod
+    def _capture(step):
+        """`step(warm)` once on a side stream outside capture (warm=True: it must leave the static x as it is), then once
+        under capture (warm=False: in place)."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):  # warm-up outside capture
+            step(True)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            step(False)
+        return graph
+
+    def _graph_store(self, key, entry):
+        self._graph_cache[key] = entry
+        self.graph_captures += 1
+        while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
+            self._graph_cache.popitem(last=False)  # least recently used graph + its buffers
+
+
+class VSampler(_CapturedSteps, Sampler):
+
+    diffusion_types = [VDiffusion]
+
+    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), use_graph: bool = True):
+        super().__init__()
+        self.net = net
+        self.schedule = schedule
+        self.use_graph = use_graph
+        self._init_graph_cache()
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
         angle = sigmas * pi / 2
@@ -303,50 +363,31 @@ class VSampler(Sampler):
         keeps the context-bank tables it was captured with alive (graphed.ctx_tables_under).
         Per step only two tiny device-to-device copies (sigma row, alpha/beta row) precede the replay.  Returns None
         (eager fallback) for kwargs that cannot be made static."""
-        from .graphed import ctx_tables_under, param_signature, tracked_parameters
-        names = sorted(kwargs)
-        live: List[Tensor] = []
-        specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
-        if any(sp is None for _, sp in specs) or any(not t.is_cuda for t in live):
+        from .graphed import ctx_tables_under
+        found = self._graph_lookup(x, kwargs, (cond is not None,))
+        if found is None:
             return None
-        key = (tuple(x.shape), x.device, specs, cond is not None)
-        psig = param_signature(tracked_parameters(self.net))
-        entry = self._graph_cache.get(key)
-        if entry is not None and entry[6] != psig:  # stale parameter addresses: drop the graph, never replay it
-            del self._graph_cache[key]
-            entry = None
+        key, names, live, psig, entry = found
         if entry is None:
             sx, ssig, sab = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(ab[0])
             scond = torch.empty_like(cond[0]) if cond is not None else None  # this step's rows of the hoisted conditioning
-            statics = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in live]
             bufs = self._step_buffers(sx)
             sx.copy_(x)
             ssig.copy_(sig[0])
             sab.copy_(ab[0])
-            for st, t in zip(statics, live):
-                st.copy_(t)
-            it = iter(statics)
-            skw = {k: _kw_rebuild(kwargs[k], it) for k in names}
+            statics, skw = self._static_kwargs(kwargs, names, live)
             if scond is not None:
                 scond.copy_(cond[0])
                 skw["conditioning"] = scond
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up outside capture
+
+            def step(warm: bool):
                 v = self.net(sx, ssig, **skw)
-                self._step(sx, v.contiguous(), sab, bufs, torch.empty_like(sx))
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                v = self.net(sx, ssig, **skw)
-                self._step(sx, v.contiguous(), sab, bufs, sx)  # in place: each element is read then written
+                # captured in place: each element is read then written
+                self._step(sx, v.contiguous(), sab, bufs, torch.empty_like(sx) if warm else sx)
+
+            graph = self._capture(step)
             entry = (graph, sx, ssig, sab, statics, scond, psig, ctx_tables_under(self.net), bufs)
-            self._graph_cache[key] = entry
-            self.graph_captures += 1
-            while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
-                self._graph_cache.popitem(last=False)  # least recently used graph + its buffers
-        else:
-            self._graph_cache.move_to_end(key)
+            self._graph_store(key, entry)
         self.graph_replays += 1
         graph, sx, ssig, sab, statics, scond = entry[:6]
         sx.copy_(x)
@@ -423,18 +464,37 @@ class Inpainter(nn.Module):
     pass
 
 
-class VInpainter(Inpainter):
+class VInpainter(_CapturedSteps, Inpainter):
     """diffusion.py:306-354.  Per resample the reference runs ~10 elementwise ops; here the rotation to the next
-    noise level, the re-noising of the source and the masked blend are ONE kernel (adp_v_inpaint_step).  The noise
-    draws stay on torch's generator (`torch.randn_like(source)`, same call order as the reference) so seeding
-    behaves identically; the (alpha, beta) table lives on the device and the loop never syncs with the host."""
+    noise level, the re-noising of the source and the masked blend are ONE kernel (adp_v_inpaint_step).  By default the
+    noise draws stay on torch's generator (`torch.randn_like(source)`, same call order as the reference) so seeding
+    behaves identically; the (alpha, beta) table lives on the device and the loop never syncs with the host.
+
+    `noise="philox"` (not in the reference) takes the noise from the library's counter-based generator instead
+    (include/adp_rng.h): `forward(..., seed=...)` fixes every draw of the run -- the start noise is draw 0, the resample
+    (i, r) uses draw 1 + i * num_resamples + r -- on any backend, and the update kernel (adp_v_inpaint_step_rng) forms the
+    noise in registers: no noise tensor is written or read.  Each resample reads one row of a device table built once per
+    run, (a_i, b_i, a_j, b_j) next to (seed_lo, seed_hi, draw, 0).
+    `use_graph=True` (philox only) captures one resample -- U-Net forward + update in place on a static x -- and replays it
+    for every (step, resample) pair behind a device-to-device copy of the pair's row, with `VSampler`'s cache rules (key,
+    recapture when parameters move, LRU, copies start empty).  It falls back to the eager loop for kwargs that cannot be
+    made static, for CPU tensors and for show_progress=True."""
 
     diffusion_types = [VDiffusion]
+    NOISE_SOURCES = ("torch", "philox")
 
-    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule()):
+    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), noise: str = "torch",
+                 use_graph: bool = False):
+        if noise not in self.NOISE_SOURCES:
+            raise ValueError(f"VInpainter: noise must be one of {self.NOISE_SOURCES}; got {noise!r}")
+        if use_graph and noise != "philox":
+            raise ValueError("VInpainter: use_graph=True needs noise='philox' (torch's generator cannot be replayed)")
         super().__init__()
         self.net = net
         self.schedule = schedule
+        self.noise = noise
+        self.use_graph = use_graph
+        self._init_graph_cache()
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
         angle = sigmas * pi / 2
@@ -442,22 +502,35 @@ class VInpainter(Inpainter):
 
     @torch.no_grad()
     def forward(self, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int, show_progress: bool = False,
-                x_noisy: Optional[Tensor] = None, **kwargs) -> Tensor:
+                x_noisy: Optional[Tensor] = None, seed: Optional[int] = None, **kwargs) -> Tensor:
+        """`seed` (noise="philox" only): the integer all draws of this run follow; None = one drawn from torch's default CPU
+        generator (so torch.manual_seed governs it), without touching the device."""
+        if self.noise != "philox":
+            if seed is not None:
+                raise ValueError("VInpainter: seed= needs noise='philox'; with noise='torch' seed torch's generator instead")
+            with _on_device_of(source):
+                return self._run(source, mask, num_steps, num_resamples, show_progress, x_noisy, kwargs)
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())  # (a CPU tensor: no device sync)
         with _on_device_of(source):
-            return self._run(source, mask, num_steps, num_resamples, show_progress, x_noisy, kwargs)
+            return self._run_philox(source, mask, num_steps, num_resamples, show_progress, x_noisy, int(seed), kwargs)
+
+    def _tables(self, num_steps: int, b: int, device):
+        """sigma table [N+1, B] and the rows (a_i, b_i, a_j, b_j) for j = i (re-noise at the same level) and j = i + 1
+        (move on), [N, 4] each, on the device."""
+        sigmas = self.schedule(num_steps + 1, device=device).to(torch.float32)
+        alphas, betas = self.get_alpha_beta(sigmas)
+        sig = sigmas[:, None].expand(num_steps + 1, b).contiguous()
+        ab_stay = torch.stack([alphas[:-1], betas[:-1], alphas[:-1], betas[:-1]], dim=1).contiguous()
+        ab_next = torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
+        return sig, ab_stay, ab_next
 
     def _run(self, source, mask, num_steps, num_resamples, show_progress, x_noisy, kwargs) -> Tensor:
         x = (x_noisy if x_noisy is not None else torch.randn_like(source)).contiguous()
         prepare = getattr(self.net, "prepare_sampling_kwargs", None)
         if prepare is not None:
             kwargs = prepare(x, kwargs)
-        b = x.shape[0]
-        sigmas = self.schedule(num_steps + 1, device=x.device).to(torch.float32)
-        alphas, betas = self.get_alpha_beta(sigmas)
-        sig = sigmas[:, None].expand(num_steps + 1, b).contiguous()
-        # rows (a_i, b_i, a_j, b_j) for j = i (re-noise at the same level) and j = i + 1 (move on)
-        ab_stay = torch.stack([alphas[:-1], betas[:-1], alphas[:-1], betas[:-1]], dim=1).contiguous()
-        ab_next = torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
+        sig, ab_stay, ab_next = self._tables(num_steps, x.shape[0], x.device)
         src = source.to(torch.float32).contiguous()
         mask_u8 = mask.expand_as(src).to(torch.uint8).contiguous()
         host_sigmas = self.schedule(num_steps + 1, device="cpu").tolist() if show_progress else None
@@ -471,3 +544,77 @@ class VInpainter(Inpainter):
             if host_sigmas is not None:
                 bar.set_description(f"Inpainting (noise={host_sigmas[i + 1]:.2f})")
         return x
+
+    def _run_philox(self, source, mask, num_steps, num_resamples, show_progress, x_noisy, seed, kwargs) -> Tensor:
+        src = source.to(torch.float32).contiguous()
+        mask_u8 = mask.expand_as(src).to(torch.uint8).contiguous()
+        dev = src.device
+        if x_noisy is not None:
+            x = x_noisy.to(torch.float32).contiguous()
+        else:
+            x = ops.randn(src, ops.rng_rows(seed, [0])[0].to(dev))
+        prepare = getattr(self.net, "prepare_sampling_kwargs", None)
+        if prepare is not None:
+            kwargs = prepare(x, kwargs)
+        sig, ab_stay, ab_next = self._tables(num_steps, x.shape[0], dev)
+        # the run's table [S, 8] (int32 words), one row per (step, resample) pair in loop order, S = num_steps * num_resamples:
+        # the bits of (a_i, b_i, a_j, b_j) f32 next to (seed_lo, seed_hi, draw, 0).  Every resample of a step but the last
+        # stays at its level.  Built once per run; the generator half comes from the host in one copy, nothing is read back.
+        total = num_steps * num_resamples
+        if total == 0:
+            return x
+        ab = ab_stay[:, None, :].repeat(1, num_resamples, 1)
+        ab[:, num_resamples - 1] = ab_next
+        rng = ops.rng_rows(seed, range(1, 1 + total)).to(dev)
+        table = torch.cat([ab.reshape(total, 4).view(torch.int32), rng], dim=1).contiguous()
+        if self.use_graph and x.is_cuda and not show_progress:
+            out = self._forward_graph(x, src, mask_u8, sig, table, num_steps, num_resamples, kwargs)
+            if out is not None:
+                return out
+        host_sigmas = self.schedule(num_steps + 1, device="cpu").tolist() if show_progress else None
+        bar = tqdm(range(num_steps), disable=not show_progress)
+        for i in bar:
+            for r in range(num_resamples):
+                v = self.net(x, sig[i], **kwargs)
+                row = table[i * num_resamples + r]
+                x = ops.v_inpaint_step_rng(x, v.contiguous(), src, mask_u8, row[:4].view(torch.float32), row[4:])
+            if host_sigmas is not None:
+                bar.set_description(f"Inpainting (noise={host_sigmas[i + 1]:.2f})")
+        return x
+
+    def _forward_graph(self, x, src, mask_u8, sig, table, num_steps, num_resamples, kwargs) -> Optional[Tensor]:
+        """One resample = U-Net forward + adp_v_inpaint_step_rng in place on the static x, captured once per call structure
+        (`_CapturedSteps`) and replayed for every (step, resample) pair.  The entry owns static copies of source, mask, the
+        sigma row, the pair's table row and every tensor kwarg; one tiny device-to-device copy (the row) precedes each
+        replay, and one more (the sigma row) when the step changes.  None = eager fallback."""
+        from .graphed import ctx_tables_under
+        found = self._graph_lookup(x, kwargs)
+        if found is None:
+            return None
+        key, names, live, psig, entry = found
+        if entry is None:
+            sx, ssig, srow = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(table[0])
+            ssrc, smask = torch.empty_like(src), torch.empty_like(mask_u8)
+            for st, t in ((sx, x), (ssig, sig[0]), (srow, table[0]), (ssrc, src), (smask, mask_u8)):
+                st.copy_(t)
+            sab, srng = srow[:4].view(torch.float32), srow[4:]
+            statics, skw = self._static_kwargs(kwargs, names, live)
+
+            def step(warm: bool):
+                v = self.net(sx, ssig, **skw)
+                # captured in place: each element is read, then written, by the lane that owns it
+                ops.v_inpaint_step_rng(sx, v.contiguous(), ssrc, smask, sab, srng, out=torch.empty_like(sx) if warm else sx)
+
+            graph = self._capture(step)
+            entry = (graph, sx, ssig, srow, statics, (ssrc, smask), psig, ctx_tables_under(self.net))
+            self._graph_store(key, entry)
+        self.graph_replays += 1
+        graph, sx, ssig, srow, statics, (ssrc, smask) = entry[:6]
+        for st, t in [(sx, x), (ssrc, src), (smask, mask_u8)] + list(zip(statics, live)):
+            st.copy_(t)
+        for i in range(num_steps):
+            ssig.copy_(sig[i])
+            for r in range(num_resamples):
+                srow.copy_(table[i * num_resamples + r])
+                graph.replay()
+        return sx.clone()

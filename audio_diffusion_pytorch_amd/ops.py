@@ -694,6 +694,69 @@ def v_inpaint_step(x: Tensor, v: Tensor, source: Tensor, noise: Tensor, mask_u8:
     return out
 
 
+# ---- include/adp_rng.h: Philox4x32-10 normals from a device (seed, draw) row
+
+def rng_rows(seed: int, draws) -> Tensor:
+    """HOST int32 table [len(draws), 4] of rows (seed_lo, seed_hi, draw, 0): the bit patterns of the uint32 words the kernels
+    read (torch has no arithmetic on uint32; the kernels take the words as they are).  seed < 2^64, each draw < 2^32."""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"rng_rows: seed must be in [0, 2^64); got {seed}")
+    rows = []
+    for d in draws:
+        d = int(d)
+        if not 0 <= d < 1 << 32:
+            raise ValueError(f"rng_rows: draw must be in [0, 2^32); got {d}")
+        rows.append([seed & 0xFFFFFFFF, seed >> 32, d, 0])
+    words = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+
+
+def _rng_row_ptr(what: str, rng4: Tensor):
+    if rng4.dtype != torch.int32 or rng4.numel() != 4:
+        raise ValueError(f"{what}: rng4 must be four int32 words (seed_lo, seed_hi, draw, 0); got {rng4.dtype} "
+                         f"{tuple(rng4.shape)}")
+    return ptr(rng4, torch.int32)
+
+
+def philox_bits(n_words: int, rng4: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The first n_words words of the row's Philox4x32-10 stream (adp_philox_bits) as int32 bit patterns."""
+    row = _rng_row_ptr("philox_bits", rng4)
+    if out is None:
+        out = torch.empty(int(n_words), dtype=torch.int32, device=rng4.device)
+    elif out.numel() != n_words:
+        raise ValueError(f"philox_bits: out must hold {n_words} words; got {out.numel()}")
+    _C.call("adp_philox_bits", row, int(n_words), ptr(out, torch.int32), _C.stream())
+    return out
+
+
+def randn(shape_like, rng4: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """N(0, 1) values of the row's stream in the shape of `shape_like` (a tensor, or a shape on rng4's device), element i of
+    the flattened tensor being normal i of the stream (adp_randn).  The same row gives the same values on every backend."""
+    row = _rng_row_ptr("randn", rng4)
+    shape = tuple(shape_like.shape) if isinstance(shape_like, Tensor) else tuple(int(s) for s in shape_like)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rng4.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"randn: out must have shape {shape}; got {tuple(out.shape)}")
+    _C.call("adp_randn", row, out.numel(), ptr(out), _C.stream())
+    return out
+
+
+def v_inpaint_step_rng(x: Tensor, v: Tensor, source: Tensor, mask_u8: Tensor, ab4: Tensor, rng4: Tensor,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """`v_inpaint_step` whose noise is the row's stream, formed in registers (adp_v_inpaint_step_rng).  `out` may be x."""
+    row = _rng_row_ptr("v_inpaint_step_rng", rng4)
+    for name, t in (("v", v), ("source", source), ("mask", mask_u8), ("out", out)):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"v_inpaint_step_rng: {name} must have x's shape {tuple(x.shape)}; got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    _C.call("adp_v_inpaint_step_rng", ptr(x), ptr(v), ptr(source), ptr(mask_u8, torch.uint8), ptr(ab4), row, x.numel(),
+            ptr(out), _C.stream())
+    return out
+
+
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
     """y2 [2B, ...] -> y2[B:] + (y2[:B] - y2[B:]) * scale."""
     half = y2.numel() // 2
