@@ -24,9 +24,7 @@ What is organised around the kernels rather than around torch ops:
   * the training step replays from hipGraphs through graphed.TrainStepGraphs, under VDiffusion's conditions;
   * the window is shifted with strided row copies (adp_copy2d) out of / into one preallocated output.
 """
-from collections import OrderedDict
-from math import pi
-from typing import Any, Callable, List, Optional, Tuple
+from typing import Any, Callable, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -36,7 +34,7 @@ from tqdm import tqdm
 
 from . import ops
 from .components import _accepts_x_append, _ConcatChannels
-from .diffusion import (Diffusion, Sampler, UniformDistribution, VDiffusion, _kw_rebuild, _kw_spec, _on_device_of,
+from .diffusion import (Diffusion, Sampler, UniformDistribution, VDiffusion, _CapturedSteps, _on_device_of, alpha_beta,
                         fused_mse_loss)
 from .models import DiffusionModel
 
@@ -71,8 +69,7 @@ class ARVDiffusion(Diffusion):
         self.two_pointer = _accepts_x_append(net)
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
-        angle = sigmas * pi / 2
-        return torch.cos(angle), torch.sin(angle)
+        return alpha_beta(sigmas)
 
     # the captured-step cache and the conditions under which it may serve a call are VDiffusion's
     train_graphs = VDiffusion.train_graphs
@@ -118,9 +115,7 @@ def _randn(shape, device, generator: Optional[Generator]) -> Tensor:
     return torch.randn(shape, generator=generator, device=generator.device).to(device)
 
 
-class ARVSampler(Sampler):
-    GRAPH_CACHE_ENTRIES = 4  # captured steps kept (LRU); each owns its private activation pool
-
+class ARVSampler(_CapturedSteps, Sampler):
     def __init__(self, net: nn.Module, in_channels: int, length: int, num_splits: int, use_graph: bool = True):
         super().__init__()
         assert length % num_splits == 0, "length must be divisible by num_splits"
@@ -131,23 +126,14 @@ class ARVSampler(Sampler):
         self.net = net
         self.use_graph = use_graph
         self.two_pointer = _accepts_x_append(net)
-        self._graph_cache: "OrderedDict" = OrderedDict()
-        self.graph_captures = 0  # (visible to tests: steps captured / loops served by replays)
-        self.graph_replays = 0
-
-    def __getstate__(self):
-        """As VSampler's: copy.deepcopy and pickling leave the captured steps behind; the copy captures its own."""
-        state = super().__getstate__()
-        state.update(_graph_cache=OrderedDict(), graph_captures=0, graph_replays=0)
-        return state
+        self._init_graph_cache()  # (graph_replays counts loops served by replays)
 
     @property
     def device(self):
         return next(self.net.parameters()).device
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
-        angle = sigmas * pi / 2
-        return torch.cos(angle), torch.sin(angle)
+        return alpha_beta(sigmas)
 
     def _ladder_splits(self, num_steps_per_split: int) -> Tensor:
         """Host [i + 1, 2 * (num_splits // 2)]: the ladder's level per step and split (diffusion.py:213-221 without the
@@ -179,52 +165,19 @@ class ARVSampler(Sampler):
             return self.net(x, x_append=plane, **kwargs).contiguous()
         return self.net(ops.concat_channels(x, plane), **kwargs).contiguous()
 
-    def _capture(self, x: Tensor, kwargs) -> Optional[tuple]:
-        """The cache entry for x's shape and this kwarg structure (VSampler._forward_graph's keying, recapture and LRU rules):
-        (graph, static x, static plane, static coefficient rows, static kwarg tensors, ...), or None (eager) for kwargs that
-        cannot be made static."""
-        from .graphed import ctx_tables_under, param_signature, tracked_parameters
-        names = sorted(kwargs)
-        live: List[Tensor] = []
-        specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
-        if any(sp is None for _, sp in specs) or any(not t.is_cuda for t in live):
-            return None
-        key = (tuple(x.shape), x.device, specs)
-        psig = param_signature(tracked_parameters(self.net))
-        entry = self._graph_cache.get(key)
-        if entry is not None and entry[5] != psig:  # stale parameter addresses: drop the graph, never replay it
-            del self._graph_cache[key]
-            entry = None
-        if entry is None:
-            b, _, t = x.shape
-            sx = torch.zeros_like(x)
-            splane = torch.zeros((b, 1, t), dtype=torch.float32, device=x.device)
-            scoef = torch.zeros((self.num_splits, 5), dtype=torch.float32, device=x.device)
-            statics = [torch.empty_like(t_, memory_format=torch.contiguous_format) for t_ in live]
-            for st, t_ in zip(statics, live):
-                st.copy_(t_)
-            it = iter(statics)
-            skw = {k: _kw_rebuild(kwargs[k], it) for k in names}
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up outside capture
-                ops.arv_step(sx, self._net_v(sx, splane, skw), scoef, out=torch.empty_like(sx),
-                             plane_out=torch.empty_like(splane))
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                # in place on x and on the plane: each element is read, then written
-                ops.arv_step(sx, self._net_v(sx, splane, skw), scoef, out=sx, plane_out=splane)
-            entry = (graph, sx, splane, scoef, statics, psig, ctx_tables_under(self.net))
-            self._graph_cache[key] = entry
-            self.graph_captures += 1
-            while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
-                self._graph_cache.popitem(last=False)  # least recently used graph + its buffers
-        else:
-            self._graph_cache.move_to_end(key)
-        for st, t_ in zip(entry[4], live):
-            st.copy_(t_)
-        return entry
+    def _build_step(self, x: Tensor, skw):
+        """`_CapturedSteps._captured_step`'s `build` for x's shape: one step = net forward + adp_arv_step."""
+        b, _, t = x.shape
+        sx = torch.zeros_like(x)
+        splane = torch.zeros((b, 1, t), dtype=torch.float32, device=x.device)
+        scoef = torch.zeros((self.num_splits, 5), dtype=torch.float32, device=x.device)
+
+        def step(warm: bool):
+            # captured in place on x and on the plane: each element is read, then written
+            ops.arv_step(sx, self._net_v(sx, splane, skw), scoef, out=torch.empty_like(sx) if warm else sx,
+                         plane_out=torch.empty_like(splane) if warm else splane)
+
+        return sx, step, dict(splane=splane, scoef=scoef)
 
     def _loop(self, x: Tensor, plane: Tensor, first: Tensor, coef: Tensor, graph, scoef, show_progress: bool, kwargs) -> None:
         """sample_loop (diffusion.py:223-238) in place on x; `plane` is the step's sigma channel."""
@@ -262,9 +215,9 @@ class ARVSampler(Sampler):
                 kwargs = prepare(x, kwargs)
             entry = None
             if self.use_graph and x.is_cuda and not show_progress:
-                entry = self._capture(x, kwargs)
+                entry = self._captured_step(x, kwargs, lambda skw: self._build_step(x, skw))
             if entry is not None:
-                graph, sx, plane, scoef = entry[:4]
+                graph, sx, plane, scoef = entry.graph, entry.sx, entry.splane, entry.scoef
                 sx.copy_(x)
                 x = sx
             else:

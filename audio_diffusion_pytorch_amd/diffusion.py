@@ -10,10 +10,9 @@ Differences from the reference are structural, not numerical:
     loop never reads device memory (the reference's tqdm f-string syncs every step, diffusion.py:188),
     so one step (U-Net forward + rotation kernel) is captured in a hipGraph and replayed.
 """
-from collections import OrderedDict
 from contextlib import nullcontext
 from math import pi
-from typing import Any, List, Optional, Tuple
+from typing import Any, Optional, Tuple
 
 import os
 
@@ -24,7 +23,10 @@ from torch import Tensor
 from tqdm import tqdm
 
 from . import ops
-
+from .capture import (CapturedStep, StepCache, ctx_tables_under, kwarg_structure, param_signature, static_kwargs,
+                      tracked_parameters, warm_up)
+from .capture import kw_spec as _kw_spec  # noqa: F401  (re-export: the name it had while it lived here)
+from .graphed import GRAPHS_OF, TrainStepGraphs
 
 
 def _on_device_of(t: Tensor):
@@ -53,6 +55,12 @@ class UniformDistribution(Distribution):
 
 def extend_dim(x: Tensor, dim: int):
     return x.view(*x.shape + (1,) * (dim - x.ndim))
+
+
+def alpha_beta(sigmas: Tensor) -> Tuple[Tensor, Tensor]:
+    """The v-objective's (alpha, beta) = (cos, sin) of sigma * pi / 2: what every `get_alpha_beta` below returns."""
+    angle = sigmas * pi / 2
+    return torch.cos(angle), torch.sin(angle)
 
 
 """ Diffusion """
@@ -108,8 +116,7 @@ class VDiffusion(Diffusion):
         self.use_graph = use_graph
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
-        angle = sigmas * pi / 2
-        return torch.cos(angle), torch.sin(angle)
+        return alpha_beta(sigmas)
 
     def forward(self, x: Tensor, noise: Optional[Tensor] = None, **kwargs) -> Tensor:
         """`noise` (optional, default torch.randn_like(x) as at diffusion.py:88) lets a harness inject the draw."""
@@ -123,7 +130,6 @@ class VDiffusion(Diffusion):
     def train_graphs(self):
         """The captured training steps of this module (kept OFF the module: hipGraphs can be neither deep-copied nor pickled,
         and an EMA copy.deepcopy(model) / torch.save(model) must keep working after a step has been captured)."""
-        from .graphed import GRAPHS_OF, TrainStepGraphs
         graphs = GRAPHS_OF.get(self)
         if graphs is None:
             graphs = GRAPHS_OF[self] = TrainStepGraphs(self)
@@ -183,40 +189,15 @@ class Sampler(nn.Module):
     pass
 
 
-def _kw_spec(value, tensors: List[Tensor]):
-    """Hashable structure of a forward kwarg (names / shapes / dtypes / python scalars -- never object identity);
-    the tensors it holds are appended to `tensors` in traversal order.  None when it cannot be made static."""
-    if isinstance(value, Tensor):
-        tensors.append(value)
-        return ("T", tuple(value.shape), value.dtype, value.device)
-    if value is None or isinstance(value, (bool, int, float)):
-        return ("S", type(value).__name__, value)
-    # (strings are NOT static: a net that takes text runs a host-side tokenizer + H2D copy per call, which is illegal
-    # inside stream capture; our own TextConditioningNet resolves text to a tensor before the loop instead)
-    if isinstance(value, (list, tuple)):
-        items = tuple(_kw_spec(v, tensors) for v in value)
-        return None if any(i is None for i in items) else ("L", type(value).__name__, items)
-    return None
-
-
-def _kw_rebuild(value, it):
-    """The same structure with every tensor replaced by the next one from `it` (the cache entry's static copy)."""
-    if isinstance(value, Tensor):
-        return next(it)
-    if isinstance(value, (list, tuple)):
-        return type(value)(_kw_rebuild(v, it) for v in value)
-    return value
-
-
 class _CapturedSteps:
-    """The cache of captured steps that `VSampler` and `VInpainter` share (mixed into an nn.Module with a `net`): one step =
-    U-Net forward + update kernel in place on a static x, captured once per call STRUCTURE and replayed.  An entry is a tuple
-    whose layout belongs to the class that builds it, except that entry[6] is the parameter signature it was captured under."""
+    """The cache of captured steps that `VSampler`, `VInpainter` and `ar.ARVSampler` share (mixed into an nn.Module with a
+    `net`): one step = net forward + update kernel in place on a static x, captured once per call STRUCTURE and replayed.
+    An entry is a `capture.CapturedStep` extended by the class that builds it; the rules are capture.py's."""
 
     GRAPH_CACHE_ENTRIES = 4  # captured steps kept (LRU); each owns its private activation pool
 
     def _init_graph_cache(self):
-        self._graph_cache: "OrderedDict" = OrderedDict()
+        self._graph_cache = StepCache()
         self.graph_captures = 0  # (visible to tests: steps captured / sampling runs served by replays)
         self.graph_replays = 0
 
@@ -224,58 +205,36 @@ class _CapturedSteps:
         """copy.deepcopy (an EMA copy) and pickling (torch.save) leave the captured steps behind: hipGraphs can be neither
         copied nor pickled, and a copy's graphs would read the original's weights.  The copy captures its own."""
         state = super().__getstate__()
-        state.update(_graph_cache=OrderedDict(), graph_captures=0, graph_replays=0)
+        state.update(_graph_cache=StepCache(), graph_captures=0, graph_replays=0)
         return state
 
-    def _graph_lookup(self, x: Tensor, kwargs, extra_key=()):
-        """None (eager fallback) for kwargs that cannot be made static, else (key, names, live, psig, entry): the cache key
-        (x shape, device, kwarg names, tensor shapes / dtypes, python scalar values, `extra_key`), the sorted kwarg names, the
-        caller's kwarg tensors in traversal order, the net's parameter signature now, and the cached entry or None.  An
-        entry whose parameters moved or were replaced is dropped here (the graph holds their addresses): never replayed."""
-        from .graphed import param_signature, tracked_parameters
-        names = sorted(kwargs)
-        live: List[Tensor] = []
-        specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
-        if any(sp is None for _, sp in specs) or any(not t.is_cuda for t in live):
+    def _captured_step(self, x: Tensor, kwargs, build, extra_key=()):
+        """The cache entry for this call structure, the caller's kwarg tensors copied into its static ones -- or None (eager
+        fallback) for kwargs that cannot be made static or hold a CPU tensor.  The key is (x shape, device, kwarg names, tensor
+        shapes / dtypes, python scalar values, `extra_key`).  A missing entry, also one dropped because the net's parameters
+        moved or were replaced, is captured: `build(skw)` takes the static kwargs and returns (static x, step, the owner's
+        static tensors by name); `step(warm)` runs once on a side stream outside capture (warm=True: it must leave the static
+        x as it is), then once under capture (warm=False: in place)."""
+        found = kwarg_structure(kwargs, lambda t: t.is_cuda)
+        if found is None:
             return None
+        names, live, specs = found
         key = (tuple(x.shape), x.device, specs) + tuple(extra_key)
         psig = param_signature(tracked_parameters(self.net))
-        entry = self._graph_cache.get(key)
-        if entry is not None and entry[6] != psig:
-            del self._graph_cache[key]
-            entry = None
-        if entry is not None:
-            self._graph_cache.move_to_end(key)
-        return key, names, live, psig, entry
-
-    @staticmethod
-    def _static_kwargs(kwargs, names, live):
-        """Static copies of the kwarg tensors (filled with the caller's values) and the kwargs rebuilt around them."""
-        statics = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in live]
-        for st, t in zip(statics, live):
+        entry = self._graph_cache.fetch(key, psig)
+        if entry is None:
+            statics, skw = static_kwargs(kwargs, names, live)
+            sx, step, own = build(skw)
+            warm_up(lambda: step(True))
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step(False)
+            entry = CapturedStep(graph, sx, statics, psig, ctx_tables_under(self.net), **own)
+            self._graph_cache.store(key, entry, self.GRAPH_CACHE_ENTRIES)
+            self.graph_captures += 1
+        for st, t in zip(entry.statics, live):
             st.copy_(t)
-        it = iter(statics)
-        return statics, {k: _kw_rebuild(kwargs[k], it) for k in names}
-
-    @staticmethod
-    def _capture(step):
-        """`step(warm)` once on a side stream outside capture (warm=True: it must leave the static x as it is), then once
-        under capture (warm=False: in place)."""
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up outside capture
-            step(True)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            step(False)
-        return graph
-
-    def _graph_store(self, key, entry):
-        self._graph_cache[key] = entry
-        self.graph_captures += 1
-        while len(self._graph_cache) > self.GRAPH_CACHE_ENTRIES:
-            self._graph_cache.popitem(last=False)  # least recently used graph + its buffers
+        return entry
 
 
 class VSampler(_CapturedSteps, Sampler):
@@ -290,8 +249,7 @@ class VSampler(_CapturedSteps, Sampler):
         self._init_graph_cache()
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
-        angle = sigmas * pi / 2
-        return torch.cos(angle), torch.sin(angle)
+        return alpha_beta(sigmas)
 
     def _tables(self, num_steps: int, b: int, device):
         """sigma table [N+1, B] and per-step (a_i, b_i, a_{i+1}, b_{i+1}) table [N, 4], both on the device.
@@ -360,22 +318,16 @@ class VSampler(_CapturedSteps, Sampler):
         tensor kwarg (also those nested in `channels`) and the caller's tensors are copied into them before the
         replays, so fresh conditioning tensors per call reuse the graph and can never be read after they are freed.
         An entry is recaptured when a parameter of the net moved or was replaced (the graph holds their addresses), and it
-        keeps the context-bank tables it was captured with alive (graphed.ctx_tables_under).
+        keeps the context-bank tables it was captured with alive (capture.py).
         Per step only two tiny device-to-device copies (sigma row, alpha/beta row) precede the replay.  Returns None
         (eager fallback) for kwargs that cannot be made static."""
-        from .graphed import ctx_tables_under
-        found = self._graph_lookup(x, kwargs, (cond is not None,))
-        if found is None:
-            return None
-        key, names, live, psig, entry = found
-        if entry is None:
+        def build(skw):
             sx, ssig, sab = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(ab[0])
             scond = torch.empty_like(cond[0]) if cond is not None else None  # this step's rows of the hoisted conditioning
             bufs = self._step_buffers(sx)
             sx.copy_(x)
             ssig.copy_(sig[0])
             sab.copy_(ab[0])
-            statics, skw = self._static_kwargs(kwargs, names, live)
             if scond is not None:
                 scond.copy_(cond[0])
                 skw["conditioning"] = scond
@@ -385,14 +337,14 @@ class VSampler(_CapturedSteps, Sampler):
                 # captured in place: each element is read then written
                 self._step(sx, v.contiguous(), sab, bufs, torch.empty_like(sx) if warm else sx)
 
-            graph = self._capture(step)
-            entry = (graph, sx, ssig, sab, statics, scond, psig, ctx_tables_under(self.net), bufs)
-            self._graph_store(key, entry)
+            return sx, step, dict(ssig=ssig, sab=sab, scond=scond, bufs=bufs)
+
+        entry = self._captured_step(x, kwargs, build, (cond is not None,))
+        if entry is None:
+            return None
         self.graph_replays += 1
-        graph, sx, ssig, sab, statics, scond = entry[:6]
+        graph, sx, ssig, sab, scond = entry.graph, entry.sx, entry.ssig, entry.sab, entry.scond
         sx.copy_(x)
-        for st, t in zip(statics, live):
-            st.copy_(t)
         for i in range(num_steps):
             if scond is not None:
                 scond.copy_(cond[i])  # (the captured step no longer reads the sigma row)
@@ -497,8 +449,7 @@ class VInpainter(_CapturedSteps, Inpainter):
         self._init_graph_cache()
 
     def get_alpha_beta(self, sigmas: Tensor) -> Tuple[Tensor, Tensor]:
-        angle = sigmas * pi / 2
-        return torch.cos(angle), torch.sin(angle)
+        return alpha_beta(sigmas)
 
     @torch.no_grad()
     def forward(self, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int, show_progress: bool = False,
@@ -587,30 +538,26 @@ class VInpainter(_CapturedSteps, Inpainter):
         (`_CapturedSteps`) and replayed for every (step, resample) pair.  The entry owns static copies of source, mask, the
         sigma row, the pair's table row and every tensor kwarg; one tiny device-to-device copy (the row) precedes each
         replay, and one more (the sigma row) when the step changes.  None = eager fallback."""
-        from .graphed import ctx_tables_under
-        found = self._graph_lookup(x, kwargs)
-        if found is None:
-            return None
-        key, names, live, psig, entry = found
-        if entry is None:
+        def build(skw):
             sx, ssig, srow = torch.empty_like(x), torch.empty_like(sig[0]), torch.empty_like(table[0])
             ssrc, smask = torch.empty_like(src), torch.empty_like(mask_u8)
             for st, t in ((sx, x), (ssig, sig[0]), (srow, table[0]), (ssrc, src), (smask, mask_u8)):
                 st.copy_(t)
             sab, srng = srow[:4].view(torch.float32), srow[4:]
-            statics, skw = self._static_kwargs(kwargs, names, live)
 
             def step(warm: bool):
                 v = self.net(sx, ssig, **skw)
                 # captured in place: each element is read, then written, by the lane that owns it
                 ops.v_inpaint_step_rng(sx, v.contiguous(), ssrc, smask, sab, srng, out=torch.empty_like(sx) if warm else sx)
 
-            graph = self._capture(step)
-            entry = (graph, sx, ssig, srow, statics, (ssrc, smask), psig, ctx_tables_under(self.net))
-            self._graph_store(key, entry)
+            return sx, step, dict(ssig=ssig, srow=srow, ssrc=ssrc, smask=smask)
+
+        entry = self._captured_step(x, kwargs, build)
+        if entry is None:
+            return None
         self.graph_replays += 1
-        graph, sx, ssig, srow, statics, (ssrc, smask) = entry[:6]
-        for st, t in [(sx, x), (ssrc, src), (smask, mask_u8)] + list(zip(statics, live)):
+        graph, sx, ssig, srow = entry.graph, entry.sx, entry.ssig, entry.srow
+        for st, t in ((sx, x), (entry.ssrc, src), (entry.smask, mask_u8)):
             st.copy_(t)
         for i in range(num_steps):
             ssig.copy_(sig[i])

@@ -29,15 +29,16 @@ object and the `UniformDistribution`'s (vmin, vmax) (both part of the cache key)
 nets under the module (attention.CtxBank; every entry keeps the tables it was captured with alive).  Any other Python-side
 state that a custom `net_t` reads in its forward is frozen at capture time as well.
 """
-import os
 import weakref
-from collections import OrderedDict
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Dict, Optional
 
 import torch
 import torch.distributed
 import torch.nn as nn
 from torch import Tensor
+
+from .capture import (StepCache, ctx_tables_under, kwarg_structure, param_signature, static_kwargs, tracked_parameters,
+                      warm_up)
 
 
 class _ProxyParameters:
@@ -65,41 +66,6 @@ class _ProxyParameters:
         return False
 
 
-def tracked_parameters(module: nn.Module) -> List[nn.Parameter]:
-    """`list(module.parameters())` without the module-tree walk (1-2 ms for ~600 parameters) on every call: the list is cached
-    on the module together with where each entry is registered and re-validated by identity per call (~30 us); replaced
-    Parameter objects (load_state_dict(assign=True), to_empty, ...) or a changed parameter count rebuild it."""
-    cache = module.__dict__.get("_adp_param_cache")
-    if cache is not None:
-        params, holders = cache
-        for p, (d, leaf) in zip(params, holders):
-            if d.get(leaf) is not p:
-                cache = None
-                break
-    if cache is None:
-        params, holders, seen = [], [], set()
-        for mod in module.modules():
-            for leaf, p in mod._parameters.items():
-                if p is not None and id(p) not in seen:
-                    seen.add(id(p))
-                    params.append(p)
-                    holders.append((mod._parameters, leaf))
-        module.__dict__["_adp_param_cache"] = (params, holders)
-    return params
-
-
-def param_signature(params) -> tuple:
-    """What a captured graph assumes about the parameters: their addresses and whether they are differentiated."""
-    return tuple((p.data_ptr(), p.requires_grad) for p in params)
-
-
-def ctx_tables_under(module: nn.Module) -> list:
-    """The context-bank pointer tables (attention.CtxBank) of every net under `module`.  A graph captured over such a net reads
-    them by address, so every captured entry holds the ones it was captured with: a net rebuilds its tables when its
-    parameters move, and the old ones must outlive every graph that still points at them."""
-    return [t for m in module.modules() if (t := m.__dict__.get("_ctx_tables")) is not None]
-
-
 class _Pending:
     """Lives on the autograd node of a replayed loss until that node's backward runs or the loss is dropped."""
     __slots__ = ("__weakref__",)
@@ -109,7 +75,7 @@ class _Entry:
     """One captured call structure: static inputs, the two graphs, the static loss / incoming gradient / parameter gradients;
     `keep` holds what the graphs read without owning it (loss_fn, context-bank tables), `pending` a weak reference to the
     _Pending token of the last replayed loss."""
-    __slots__ = ("g_f", "g_b", "sx", "snoise", "statics", "sloss", "sgloss", "params", "grads", "sig", "step", "keep",
+    __slots__ = ("g_f", "g_b", "sx", "snoise", "statics", "sloss", "sgloss", "params", "grads", "psig", "step", "keep",
                  "pending")
 
 
@@ -154,18 +120,16 @@ class TrainStepGraphs:
 
     def __init__(self, owner: nn.Module):
         self._owner = weakref.ref(owner)  # (the registry below is keyed weakly on the owner: no cycle through this object)
-        self.cache: "OrderedDict[Any, _Entry]" = OrderedDict()
+        self.cache = StepCache()  # key -> _Entry
         self.eager_only: Dict[Any, Any] = {}  # key -> its loss_fn (held: the key names it by id)
         self.captures = 0  # (visible to tests / bench: how many times a step was captured)
         self.replays = 0
 
     def run(self, x: Tensor, noise: Optional[Tensor], kwargs: Dict[str, Any]) -> Optional[Tensor]:
-        from .diffusion import _kw_spec
-        names = sorted(kwargs)
-        live: List[Tensor] = []
-        specs = tuple((k, _kw_spec(kwargs[k], live)) for k in names)
-        if any(sp is None for _, sp in specs) or any((not t.is_cuda) or t.requires_grad for t in live):
+        found = kwarg_structure(kwargs, lambda t: t.is_cuda and not t.requires_grad)
+        if found is None:
             return None
+        names, live, specs = found
         owner = self._owner()
         loss_fn, dist = owner.loss_fn, owner.sigma_distribution
         # (the captured step calls this loss_fn and draws sigmas from these bounds; the entry holds loss_fn, so its id is unique)
@@ -173,11 +137,8 @@ class TrainStepGraphs:
         if key in self.eager_only:
             return None
         all_params = tracked_parameters(owner)
-        sig = param_signature(all_params)
-        entry = self.cache.get(key)
-        if entry is not None and entry.sig != sig:  # parameters moved / replaced / (un)frozen: the graph holds stale pointers
-            del self.cache[key]
-            entry = None
+        psig = param_signature(all_params)
+        entry = self.cache.fetch(key, psig)  # (None also when parameters moved / were replaced / (un)frozen)
         if entry is not None and entry.pending is not None and entry.pending() is not None:
             return None  # a replayed loss of this entry still waits for its backward, which needs the activations: run eagerly
         if entry is None:
@@ -196,14 +157,10 @@ class TrainStepGraphs:
                 self.eager_only[key] = loss_fn
                 torch.cuda.synchronize(x.device)
                 return None
-            entry.sig = sig
+            entry.psig = psig
             entry.keep = (loss_fn, ctx_tables_under(owner))
             entry.pending = None
-            self.cache[key] = entry
-            while len(self.cache) > self.MAX_ENTRIES:
-                self.cache.popitem(last=False)
-        else:
-            self.cache.move_to_end(key)
+            self.cache.store(key, entry, self.MAX_ENTRIES)
         entry.sx.copy_(x)
         if noise is not None:
             entry.snoise.copy_(noise)
@@ -213,30 +170,26 @@ class TrainStepGraphs:
         return _Replay.apply(entry, *entry.params)
 
     def _capture(self, x, noise, kwargs, names, live, params) -> _Entry:
-        from .diffusion import _kw_rebuild
         eager = self._owner()._forward_eager  # (x, noise, **kwargs) -> loss: the un-captured step
         e = _Entry()
         e.sx = x.detach().contiguous().clone()
         e.snoise = noise.detach().contiguous().clone() if noise is not None else None
-        e.statics = [t.detach().clone(memory_format=torch.contiguous_format) for t in live]
-        it = iter(e.statics)
-        skw = {k: _kw_rebuild(kwargs[k], it) for k in names}
+        e.statics, skw = static_kwargs(kwargs, names, live)
         e.sgloss = torch.ones((), dtype=torch.float32, device=x.device)
         e.params = params
         dev = x.device
         # two eager steps on a side stream (allocator pools, lazily built tables); they must not be seen by the caller: no
         # .grad is touched (autograd.grad) and the generator is put back, so a seeded script draws what the eager loop draws
-        rng = torch.cuda.get_rng_state(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        def two_steps():
             for _ in range(2):
                 loss = eager(e.sx, e.snoise, **skw)
                 if loss.dim() != 0:
                     raise ValueError("the loss is not a scalar")
                 torch.autograd.grad(loss, params, grad_outputs=e.sgloss, allow_unused=True)
                 del loss
-        torch.cuda.current_stream(dev).wait_stream(side)
+
+        rng = torch.cuda.get_rng_state(dev)
+        warm_up(two_steps, dev)
         torch.cuda.synchronize(dev)
         torch.cuda.set_rng_state(rng, dev)
         # inside a process group (e.g. under torch's DistributedDataParallel): its watchdog thread queries the events of earlier

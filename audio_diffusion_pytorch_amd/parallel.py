@@ -18,6 +18,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .capture import warm_up
+
 
 def graph_safe_rccl_env() -> None:
     """Environment under which a training step WITH its RCCL all-reduces can be captured in a hipGraph (set before the
@@ -53,12 +55,11 @@ def capture_step(step, warmup: int = 2):
     default "global" mode an event query from ANY thread aborts the process (seen once in five runs of the `dp1` leg); works
     issued under capture are not handed to the watchdog at all.  Call with gradients set to None (the captured AccumulateGrad
     then adopts views of the flat gradient buffer, as in the eager step)."""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
+    def warm():
         for _ in range(warmup):
             step()
-    torch.cuda.current_stream().wait_stream(side)
+
+    warm_up(warm)
     quiesce_watchdog()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -73,13 +74,12 @@ def capture_step_deferred(step, dp: "DataParallel", warmup: int = 2):
     per-kernel host launches either (an eager data-parallel step is host bound at ~2x the kernels' time).  Returns (graph, replay)."""
     dp._deferred = []
     try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def warm():
             for _ in range(warmup):
                 step()
                 dp.flush_deferred()
-        torch.cuda.current_stream().wait_stream(side)
+
+        warm_up(warm)
         quiesce_watchdog()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):

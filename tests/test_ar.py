@@ -370,6 +370,42 @@ def test_sampler_replays_one_captured_step(hip):
 
 
 @pytest.mark.gpu
+def test_sampler_recaptures_moved_parameters_and_bounds_its_cache(hip):
+    """The shared cache rules on ARVSampler: a graph over dead parameter addresses is never replayed, and the cache is an LRU of
+    GRAPH_CACHE_ENTRIES captured steps."""
+    model = _gpu_model(hip)
+    s = model.sampler
+
+    def run(use_graph, num_items=2):
+        s.use_graph = use_graph
+        return model.sample(num_items=num_items, num_chunks=9, num_steps=8, generator=torch.Generator().manual_seed(1))
+
+    out = run(True)
+    assert s.graph_captures == 1 and len(s._graph_cache) == 1
+    # new weights in fresh storage (allocated while the old storage is alive): the old graph holds dead addresses
+    gen = torch.Generator().manual_seed(4)
+    sd = {k: v + 0.05 * v.abs().mean() * torch.randn(v.shape, generator=gen).to(v.device)
+          for k, v in model.net.state_dict().items()}
+    model.net.load_state_dict(sd, assign=True)
+    out_new = run(True)
+    assert s.graph_captures == 2 and len(s._graph_cache) == 1, "the stale entry was not recaptured"
+    err = rel_err(out_new, run(False))
+    print(f"recaptured against eager on the new weights: rel err {err:.3e}")
+    assert err < 1e-5
+    assert not torch.equal(out_new, out)
+    del sd
+
+    # the bound, on a sampler of its own: five batch sizes are five call structures
+    model = _gpu_model(hip)
+    s = model.sampler
+    for b in range(1, 6):
+        run(True, num_items=b)
+    assert s.graph_captures == 5 and len(s._graph_cache) == _ar().ARVSampler.GRAPH_CACHE_ENTRIES
+    run(True, num_items=1)
+    assert s.graph_captures == 6, "num_items=1 was the least recently used entry: evicted, captured again"
+
+
+@pytest.mark.gpu
 def test_training_step_replays_and_equals_the_eager_step(hip):
     m_g, m_e = _gpu_model(hip), _gpu_model(hip, diffusion_use_graph=False)
     g = torch.Generator().manual_seed(9)

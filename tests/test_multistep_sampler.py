@@ -267,7 +267,7 @@ def test_replay_equals_eager(hip):
     # a run from NaN leaves NaN in the entry's history buffers; the next run must not see it
     poisoned = m_g.sample(torch.full_like(noise, float("nan")), num_steps=3)
     assert torch.isnan(poisoned).all()
-    assert all(torch.isnan(b).all() for b in next(iter(m_g.sampler._graph_cache.values()))[8])
+    assert all(torch.isnan(b).all() for b in next(iter(m_g.sampler._graph_cache.values())).bufs)
     out = m_g.sample(noise2, num_steps=5)
     assert torch.isfinite(out).all() and torch.equal(out, m_e.sample(noise2, num_steps=5))
     assert m_g.sampler.graph_captures == 1
@@ -349,7 +349,7 @@ def test_classifier_free_guidance(hip):
     out = model.sample(x.to(hip), num_steps=4, embedding=emb.to(hip), embedding_scale=2.0)
     ref = multistep_ref(lambda xx, tt: oracle(xx, tt, embedding=emb, embedding_scale=2.0), x, 4)
     assert model.sampler.graph_captures == 1
-    assert all(b.shape == x.shape for b in next(iter(model.sampler._graph_cache.values()))[8])
+    assert all(b.shape == x.shape for b in next(iter(model.sampler._graph_cache.values())).bufs)
     assert rel_err(out, ref) <= PARITY_TOL
 
 
