@@ -13,6 +13,12 @@ namespace {
 
 constexpr int GN_CHUNK = 4096;  // elements per partial-statistics workgroup (16 per thread, register resident)
 
+// every one of these operands that is there (null: absent) sits on a 16-byte boundary -- what the float4 forms ask for
+template <class... P>
+bool aligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 15) == 0;
+}
+
 // ---- GroupNorm statistics: chunk-local (mean, M2) then Chan's exact combination ------------------------
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* x, int64_t NG, int64_t nchunks, float* ws) {
   __shared__ float sh[4];
@@ -543,13 +549,33 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_vec_kernel(const float* __re
   }
 }
 
-// threads per (row, split) segment of the vector form: one float4 per lane up to a wave, the whole workgroup beyond
-static int gn_bwd_tpr(int64_t CL) { return CL <= 64 ? 16 : (CL <= 128 ? 32 : (CL <= 1024 ? 64 : 256)); }
-static bool gn_bwd_vec_ok(const float* x, const float* dact, const float* dres, const float* dx, int64_t L, int64_t CL) {
-  return (L & 3) == 0 && (CL & 3) == 0 &&
-         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dact) | reinterpret_cast<uintptr_t>(dres) |
-           reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
+// What both stages of the backward launch: the segment length they share (one derivation from L and NS), the form, and for the
+// vector form the threads per (row, split) segment -- one float4 per lane up to a wave, the whole workgroup beyond.
+struct GnBwdPlan {
+  int64_t CL, nseg;  // positions per (row, split) segment; segments
+  bool vec;          // 16-byte form (gn_bwd_*_vec_kernel<tpr>) or row form (one workgroup per segment)
+  int tpr;
+  dim3 grid;
+};
+GnBwdPlan gn_bwd_plan(int64_t B, int64_t C, int64_t L, int64_t NS, const float* x, const float* dact, const float* dres,
+                      const float* dx, const float* ab) {
+  GnBwdPlan p;
+  p.CL = adp_cdiv(L, NS);
+  if ((L & 3) == 0) p.CL = (p.CL + 3) & ~(int64_t)3;
+  p.nseg = B * C * NS;
+  p.vec = (L & 3) == 0 && (p.CL & 3) == 0 && aligned16(x, dact, dres, dx) && (reinterpret_cast<uintptr_t>(ab) & 7) == 0;
+  p.tpr = p.CL <= 64 ? 16 : (p.CL <= 128 ? 32 : (p.CL <= 1024 ? 64 : 256));
+  p.grid = p.vec ? dim3((unsigned)adp_cdiv(p.nseg, 256 / p.tpr)) : dim3((unsigned)NS, (unsigned)(B * C));
+  return p;
 }
+// the vector-form kernel for the plan's threads per segment
+#define ADP_GN_BWD_VEC(KERNEL, p, stream, ...)                                                   \
+  switch ((p).tpr) {                                                                              \
+    case 16: ADP_LAUNCH((KERNEL<16>), (p).grid, dim3(256), stream, __VA_ARGS__); break;           \
+    case 32: ADP_LAUNCH((KERNEL<32>), (p).grid, dim3(256), stream, __VA_ARGS__); break;           \
+    case 64: ADP_LAUNCH((KERNEL<64>), (p).grid, dim3(256), stream, __VA_ARGS__); break;           \
+    default: ADP_LAUNCH((KERNEL<256>), (p).grid, dim3(256), stream, __VA_ARGS__);                 \
+  }
 
 __global__ __launch_bounds__(256) void gn_param_grad_kernel(const float* ab, int64_t B, int64_t C, int64_t NS,
                                                             float* dgamma, float* dbeta, int accumulate) {
@@ -725,6 +751,12 @@ __global__ __launch_bounds__(NT) void chan_ln_bwd_kernel(const float* x, const f
 // from ONE lane each instead of 4 lanes x 4 bytes.  Reductions: per position over channels = xor-shuffles across the
 // row groups of a wave + one LDS round across waves; per channel over the tile's positions (backward) = the lane's four
 // components + xor-shuffles across the LPR lanes of the segment.
+// the (mean, rstd) pairs of four consecutive positions: two float4 of the statistics tensor
+__device__ __forceinline__ void ln_stats_load4(const float* sp, float (&mean)[4], float (&rstd)[4]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(sp), c4 = *reinterpret_cast<const f32x4*>(sp + 4);
+  mean[0] = a[0], rstd[0] = a[1], mean[1] = a[2], rstd[1] = a[3];
+  mean[2] = c4[0], rstd[2] = c4[1], mean[3] = c4[2], rstd[3] = c4[3];
+}
 template <int LPR, int NT, int VPT>
 __global__ __launch_bounds__(NT) void chan_lnv_fwd_kernel(const float* x, const float* ss, int64_t bstride, int C, int L,
                                                           float eps, float* y, float* stats, const float* gam,
@@ -893,10 +925,7 @@ __global__ __launch_bounds__(NT) void chan_lnv_bwd_kernel(const float* x, const 
   const int64_t boff = (int64_t)b * C * L + l0;
   float mean[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rstd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (valid) {
-    const float* sp = stats + ((int64_t)b * L + l0) * 2;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(sp), c4 = *reinterpret_cast<const f32x4*>(sp + 4);
-    mean[0] = a[0], rstd[0] = a[1], mean[1] = a[2], rstd[1] = a[3];
-    mean[2] = c4[0], rstd[2] = c4[1], mean[3] = c4[2], rstd[3] = c4[3];
+    ln_stats_load4(stats + ((int64_t)b * L + l0) * 2, mean, rstd);
   }
   f32x4 xh[VPT], g[VPT];
   float s1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1007,14 +1036,8 @@ __global__ __launch_bounds__(NT) void chan_lnv_bwd_chain_kernel(const float* x, 
   float mean1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rstd1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float mean2[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rstd2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (valid) {
-    const float* sp = stats1 + ((int64_t)b * L + l0) * 2;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(sp), c4 = *reinterpret_cast<const f32x4*>(sp + 4);
-    mean1[0] = a[0], rstd1[0] = a[1], mean1[1] = a[2], rstd1[1] = a[3];
-    mean1[2] = c4[0], rstd1[2] = c4[1], mean1[3] = c4[2], rstd1[3] = c4[3];
-    const float* sq = stats2 + ((int64_t)b * L + l0) * 2;
-    const f32x4 e = *reinterpret_cast<const f32x4*>(sq), f4 = *reinterpret_cast<const f32x4*>(sq + 4);
-    mean2[0] = e[0], rstd2[0] = e[1], mean2[1] = e[2], rstd2[1] = e[3];
-    mean2[2] = f4[0], rstd2[2] = f4[1], mean2[3] = f4[2], rstd2[3] = f4[3];
+    ln_stats_load4(stats1 + ((int64_t)b * L + l0) * 2, mean1, rstd1);
+    ln_stats_load4(stats2 + ((int64_t)b * L + l0) * 2, mean2, rstd2);
   }
   const float* sb = ss + b * bstride;
   f32x4 xh[VPT], g[VPT];
@@ -1134,147 +1157,157 @@ __global__ __launch_bounds__(NT) void chan_lnv_bwd_chain_kernel(const float* x, 
   }
 }
 
-// vector-form tile by channel count: (lanes per row segment, threads, passes); RPP * VPT >= C
-struct LnvCfg {
-  int lpr, nt, vpt;
+// ---- which tile a channel-LayerNorm launch takes: one plan, one list of (segment, threads, passes) per form ----------------
+#define ADP_LNV_TILES(X)                                                                                            \
+  X(64, 256, 2) X(32, 256, 4) X(16, 256, 4) X(8, 256, 4) X(8, 1024, 2) X(4, 1024, 2) X(2, 1024, 1) X(4, 1024, 4) \
+  X(2, 1024, 2) X(1, 1024, 1) X(4, 512, 4) X(4, 512, 8) X(2, 512, 2) X(2, 512, 4) X(1, 512, 2) X(8, 512, 4)
+#define ADP_LN_TILES(X) \
+  X(64, 256, 2) X(64, 256, 8) X(64, 256, 16) X(32, 256, 16) X(32, 1024, 8) X(16, 1024, 16) X(8, 1024, 8) X(4, 1024, 4)
+
+constexpr int64_t LN_CMAX = 1024;
+
+struct LnPlan {
+  bool vec;     // 16-byte form (chan_lnv_*: L % 4 == 0 and aligned operands) or 4-byte form (chan_ln_*)
+  int seg;      // row segment of a tile: LPR lanes of four positions each (vec) or TL positions
+  int nt, vpt;  // threads and passes: (nt / seg) rows per pass * vpt passes >= C
+  int ntl;      // position tiles: the grid's x extent, and the tile count of the backward's partial channel sums
 };
-static LnvCfg lnv_cfg(int64_t C, int64_t B, int64_t L, bool bwd = false) {
-  if (C <= 8) return {64, 256, 2};     // 1 KB row segments, 4 rows per pass
-  if (C <= 32) return {32, 256, 4};    // 512 B, 8 rows per pass
-  if (C <= 64) return {16, 256, 4};    // 256 B, 16 rows per pass
-  if (C <= 128) return {8, 256, 4};    // 128 B, 32 rows per pass
-  if (C <= 256) {  // 128 B segments; 512 threads x 4 passes (1024 x 2 before round 4: ADP_LNV_NT=1024)
-    if (adp_knob(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT", 512) == 1024) return {8, 1024, 2};
-    return {8, 512, 4};
+
+// The tile by channel count and by how many tiles there are.  knob_nt: ADP_LNV_NT (forward) / ADP_LNV_NT_BWD (backward), read by
+// ln_plan below; 1024 brings back the 1024-thread shapes of the 16-byte form (A/B), anything else is the default.
+constexpr LnPlan ln_plan_at(int64_t C, int64_t B, int64_t L, bool vec, int64_t knob_nt) {
+  LnPlan p{vec, 0, 0, 0, 0};
+  const bool nt1024 = knob_nt == 1024;
+  if (vec) {
+    if (C <= 8) p.seg = 64, p.nt = 256, p.vpt = 2;          // 1 KB row segments, 4 rows per pass
+    else if (C <= 32) p.seg = 32, p.nt = 256, p.vpt = 4;    // 512 B, 8 rows per pass
+    else if (C <= 64) p.seg = 16, p.nt = 256, p.vpt = 4;    // 256 B, 16 rows per pass
+    else if (C <= 128) p.seg = 8, p.nt = 256, p.vpt = 4;    // 128 B, 32 rows per pass
+    else if (C <= 256) {  // 128 B segments; 512 threads x 4 passes (1024 x 2 before round 4: the knob)
+      p.seg = 8, p.nt = nt1024 ? 1024 : 512, p.vpt = nt1024 ? 2 : 4;
+    } else {
+      // 512 / 1024 channels: few positions (depth 8 at batch 4: 512), so the segment narrows until enough workgroups exist
+      // (measured at batch 4, step time: 16 positions 14.38 ms, 8 positions 14.42, 4 positions 14.53)
+      int lpr = 4;
+      while (lpr > 1 && B * ((L + 4 * lpr - 1) / (4 * lpr)) < 32) lpr >>= 1;
+      if (C <= 512 && lpr == 1) lpr = 2;  // (no 4-position tile is built for 512 channels)
+      // 512-thread workgroups, twice the passes in registers (round 4; hipGraph per-launch us at batch 4, 1024 -> 512 threads:
+      // forward C=512 L=1024 9.7 -> 8.0, L=512 6.9 -> 5.6, C=1024 7.4 -> 6.6 / 7.1 -> 6.3; backward 14.0 -> 12.9, 10.9 -> 9.9,
+      // 12.5 -> 12.3, 9.3 -> 9.1: an 8-wave barrier and 8 partials per reduction instead of 16; 256 threads x 16 passes lose
+      // again).  The knob's 1024 threads are the previous shape.  Passes: nt / lpr rows each, to cover 512 or 1024 channels.
+      p.seg = lpr, p.nt = nt1024 ? 1024 : 512;
+      p.vpt = (C <= 512 ? 512 : 1024) * lpr / p.nt;
+    }
+  } else {
+    // registers: VPT = ceil(C / CG) values per thread, CG = nt / seg channel groups
+    if (C <= 64) p.seg = 64, p.nt = 256, p.vpt = C <= 8 ? 2 : (C <= 32 ? 8 : 16);  // CG 4
+    else if (C <= 128) p.seg = 32, p.nt = 256, p.vpt = 16;                          // CG 8
+    else if (C <= 256) p.seg = 32, p.nt = 1024, p.vpt = 8;                          // CG 32
+    // C <= 1024, 1024-thread workgroups: the deep layers have few positions (depth 8 at batch 4: 512), so the tile
+    // narrows until the grid covers the chip -- 16 positions (CG 64, VPT 16), 8 (CG 128, VPT 8) or 4 (CG 256, VPT 4)
+    else if (B * ((L + 15) / 16) >= 192) p.seg = 16, p.nt = 1024, p.vpt = 16;
+    else if (B * ((L + 7) / 8) >= 192) p.seg = 8, p.nt = 1024, p.vpt = 8;
+    else p.seg = 4, p.nt = 1024, p.vpt = 4;
   }
-  // 512 / 1024 channels, 1024-thread workgroups: few positions (depth 8 at batch 4: 512), so the segment narrows until
-  // enough workgroups exist (measured at batch 4, step time: 16 positions 14.38 ms, 8 positions 14.42, 4 positions 14.53)
-  int lpr = 4;
-  while (lpr > 1 && B * adp_cdiv(L, 4 * lpr) < 32) lpr >>= 1;  // (batch 4: 16 positions at depths 5-8 measured best)
-  // 512-thread workgroups, twice the passes in registers (round 4; hipGraph per-launch us at batch 4, 1024 -> 512 threads:
-  // forward C=512 L=1024 9.7 -> 8.0, L=512 6.9 -> 5.6, C=1024 7.4 -> 6.6 / 7.1 -> 6.3; backward 14.0 -> 12.9, 10.9 -> 9.9, 12.5 ->
-  // 12.3, 9.3 -> 9.1: an 8-wave barrier and 8 partials per reduction instead of 16; 256 threads x 16 passes lose again).
-  // ADP_LNV_NT / ADP_LNV_NT_BWD = 1024: the previous shape (A/B).
-  if (adp_knob(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT", 512) != 1024) {
-    const int lp = (C <= 512 && lpr == 1) ? 2 : lpr;
-    return {lp, 512, C <= 512 ? lp : 2 * lp};
-  }
-  if (C <= 512) return {lpr == 1 ? 2 : lpr, 1024, lpr == 4 ? 2 : 1};
-  return {lpr, 1024, lpr};  // RPP = 1024 / lpr rows per pass -> lpr passes cover 1024 channels
+  const int64_t tl = vec ? 4 * p.seg : p.seg;
+  p.ntl = (int)((L + tl - 1) / tl);
+  return p;
 }
-static bool lnv_ok(int64_t L, const void* a, const void* b, const void* c, const void* d, const void* e) {
-  return (L & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                           reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(e)) & 15) == 0;
+// the plan of a launch: the forward and the backward read their own knob; aligned: every tensor operand on 16 bytes
+LnPlan ln_plan(int64_t C, int64_t B, int64_t L, bool bwd, bool aligned) {
+  return ln_plan_at(C, B, L, aligned && (L & 3) == 0, adp_knob(bwd ? "ADP_LNV_NT_BWD" : "ADP_LNV_NT", 512));
 }
 
-// tile shape by channel count (registers: VPT = ceil(C / CG) values per thread) and by how many tiles there are
-struct LnCfg {
-  int tl, nt;
-};
-LnCfg ln_cfg(int64_t C, int64_t B, int64_t L) {
-  if (C <= 64) return {64, 256};     // CG 4,  VPT 2 / 8 / 16
-  if (C <= 128) return {32, 256};    // CG 8,  VPT 16
-  if (C <= 256) return {32, 1024};   // CG 32, VPT 8
-  // C <= 1024, 1024-thread workgroups: the deep layers have few positions (depth 8 at batch 4: 512), so the tile
-  // narrows until the grid covers the chip -- 16 positions (CG 64, VPT 16), 8 (CG 128, VPT 8) or 4 (CG 256, VPT 4)
-  if (B * adp_cdiv(L, 16) >= 192) return {16, 1024};
-  if (B * adp_cdiv(L, 8) >= 192) return {8, 1024};
-  return {4, 1024};
+constexpr bool ln_tile_listed(const LnPlan& p) {
+#define ADP_LN_IS(S, NT, VPT) \
+  if (p.seg == S && p.nt == NT && p.vpt == VPT) return true;
+  if (p.vec) {
+    ADP_LNV_TILES(ADP_LN_IS)
+  } else {
+    ADP_LN_TILES(ADP_LN_IS)
+  }
+#undef ADP_LN_IS
+  return false;
 }
-constexpr int64_t LN_CMAX = 1024;
+// Every plan there is (the direction only chooses the knob, so the two knob values stand for both directions): each channel
+// count, at (B, L) on every side of the narrowing thresholds, names a listed tile whose passes cover C, every width is reached.
+constexpr bool ln_plans_listed(bool vec, int64_t knob_nt) {
+  constexpr int64_t BL[5][2] = {{4, 768}, {4, 384}, {4, 128}, {1, 256}, {1, 16}};
+  int widths = 0;
+  for (const auto& bl : BL)
+    for (int64_t C = 1; C <= LN_CMAX; ++C) {
+      const LnPlan p = ln_plan_at(C, bl[0], bl[1], vec, knob_nt);
+      if (!ln_tile_listed(p) || (int64_t)(p.nt / p.seg) * p.vpt < C) return false;
+      if (C == LN_CMAX) widths |= p.seg;
+    }
+  return widths == (vec ? (4 | 2 | 1) : (16 | 8 | 4));
+}
+static_assert(ln_plans_listed(true, 512) && ln_plans_listed(true, 1024), "16-byte form: a planned tile is not instantiated");
+static_assert(ln_plans_listed(false, 512) && ln_plans_listed(false, 1024), "4-byte form: a planned tile is not instantiated");
+
+// One launcher per kernel template; ln_launch_vec / ln_launch_row call the one the plan names, looked up in the form's list.
+#define ADP_LN_LAUNCHER(NAME, KERNEL)                                                                                       \
+  template <int S, int NT, int VPT>                                                                                         \
+  struct NAME {                                                                                                             \
+    template <class... A>                                                                                                   \
+    static void launch(dim3 grid, void* stream, A... a) { ADP_LAUNCH((KERNEL<S, NT, VPT>), grid, dim3(NT), stream, a...); } \
+  };
+ADP_LN_LAUNCHER(LnvFwd, chan_lnv_fwd_kernel)
+ADP_LN_LAUNCHER(LnvBwd, chan_lnv_bwd_kernel)
+ADP_LN_LAUNCHER(LnvBwdChain, chan_lnv_bwd_chain_kernel)
+ADP_LN_LAUNCHER(LnFwd, chan_ln_fwd_kernel)
+ADP_LN_LAUNCHER(LnBwd, chan_ln_bwd_kernel)
+#undef ADP_LN_LAUNCHER
+
+#define ADP_LN_CASE(S, NT, VPT) \
+  if (p.seg == S && p.nt == NT && p.vpt == VPT) return K<S, NT, VPT>::launch(grid, stream, a...), ADP_OK;
+template <template <int, int, int> class K, class... A>
+int ln_launch_vec(const LnPlan& p, int64_t B, void* stream, A... a) {
+  const dim3 grid((unsigned)p.ntl, (unsigned)B);
+  ADP_LNV_TILES(ADP_LN_CASE)
+  return ADP_ERR_UNSUPPORTED;
+}
+template <template <int, int, int> class K, class... A>
+int ln_launch_row(const LnPlan& p, int64_t B, void* stream, A... a) {
+  const dim3 grid((unsigned)p.ntl, (unsigned)B);
+  ADP_LN_TILES(ADP_LN_CASE)
+  return ADP_ERR_UNSUPPORTED;
+}
+#undef ADP_LN_CASE
+
+int ln_shape_check(int64_t B, int64_t C, int64_t L) {
+  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
+  return C > LN_CMAX ? ADP_ERR_UNSUPPORTED : ADP_OK;
+}
 
 int launch_ln_fwd(const float* x, const float* ss, int64_t bstride, int64_t B, int64_t C, int64_t L, float eps, float* y,
                   float* stats, void* stream, const float* gam = nullptr, const float* bet = nullptr,
                   const float* gam2 = nullptr, const float* bet2 = nullptr, float* y2 = nullptr, float eps2 = 0.0f,
                   float* cy = nullptr, float* cstats = nullptr) {
-  if (cy && !(lnv_ok(L, x, y, y2, stats, cy) && lnv_ok(L, cstats, nullptr, nullptr, nullptr, nullptr))) {
+  const LnPlan p = ln_plan(C, B, L, false, aligned16(x, y, y2, stats, cy, cstats));
+  if (cy && !p.vec) {
     // chained Modulation -> LayerNorm without the 16-byte form: the two launches it stands for
     const int rc = launch_ln_fwd(x, ss, bstride, B, C, L, eps, y, stats, stream);
     if (rc != ADP_OK) return rc;
     return launch_ln_fwd(y, nullptr, 0, B, C, L, eps2, cy, cstats, stream, gam, bet, gam2, bet2, y2);
   }
-  if (lnv_ok(L, x, y, y2, stats, nullptr)) {
-    const LnvCfg v = lnv_cfg(C, B, L);
-    dim3 vgrid((unsigned)adp_cdiv(L, 4 * v.lpr), (unsigned)B);
-#define ADP_LNV_FWD(LPR, NT, VPT)                                                                                     \
-  if (v.lpr == LPR && v.nt == NT && v.vpt == VPT) {                                                                   \
-    ADP_LAUNCH((chan_lnv_fwd_kernel<LPR, NT, VPT>), vgrid, dim3(NT), stream, x, ss, bstride, (int)C, (int)L, eps, y, \
-               stats, gam, bet, gam2, bet2, y2, eps2, cy, cstats);                                                    \
-    return ADP_LAUNCH_OK();                                                                                           \
-  }
-    ADP_LNV_FWD(64, 256, 2) ADP_LNV_FWD(32, 256, 4) ADP_LNV_FWD(16, 256, 4) ADP_LNV_FWD(8, 256, 4) ADP_LNV_FWD(8, 1024, 2)
-    ADP_LNV_FWD(4, 1024, 2) ADP_LNV_FWD(2, 1024, 1) ADP_LNV_FWD(4, 1024, 4) ADP_LNV_FWD(2, 1024, 2) ADP_LNV_FWD(1, 1024, 1)
-    ADP_LNV_FWD(4, 512, 4) ADP_LNV_FWD(4, 512, 8) ADP_LNV_FWD(2, 512, 2) ADP_LNV_FWD(2, 512, 4) ADP_LNV_FWD(1, 512, 2) ADP_LNV_FWD(8, 512, 4)
-#undef ADP_LNV_FWD
-  }
-  const LnCfg k = ln_cfg(C, B, L);
-  dim3 grid((unsigned)adp_cdiv(L, k.tl), (unsigned)B);
-  if (k.tl == 8)
-    ADP_LAUNCH((chan_ln_fwd_kernel<8, 1024, 8>), grid, dim3(1024), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 4)
-    ADP_LAUNCH((chan_ln_fwd_kernel<4, 1024, 4>), grid, dim3(1024), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 64 && C <= 8)
-    ADP_LAUNCH((chan_ln_fwd_kernel<64, 256, 2>), grid, dim3(256), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 64 && C <= 32)
-    ADP_LAUNCH((chan_ln_fwd_kernel<64, 256, 8>), grid, dim3(256), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 64)
-    ADP_LAUNCH((chan_ln_fwd_kernel<64, 256, 16>), grid, dim3(256), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 32 && k.nt == 256)
-    ADP_LAUNCH((chan_ln_fwd_kernel<32, 256, 16>), grid, dim3(256), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else if (k.tl == 32)
-    ADP_LAUNCH((chan_ln_fwd_kernel<32, 1024, 8>), grid, dim3(1024), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  else
-    ADP_LAUNCH((chan_ln_fwd_kernel<16, 1024, 16>), grid, dim3(1024), stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2, bet2, y2);
-  return ADP_LAUNCH_OK();
+  const int rc = p.vec ? ln_launch_vec<LnvFwd>(p, B, stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2,
+                                               bet2, y2, eps2, cy, cstats)
+                       : ln_launch_row<LnFwd>(p, B, stream, x, ss, bstride, (int)C, (int)L, eps, y, stats, gam, bet, gam2,
+                                              bet2, y2);
+  return rc != ADP_OK ? rc : ADP_LAUNCH_OK();
 }
 
-// returns the number of position tiles the launch wrote partial channel sums for (ws [b][2][tile][c])
+// returns the number of position tiles the launch wrote partial channel sums for (ws [b][2][tile][c]), or an error code
 int launch_ln_bwd(const float* x, const float* dy, const float* ss, int64_t bstride, const float* gamma,
                   const float* stats, const float* dres, int64_t B, int64_t C, int64_t L, float* dx, float* ws,
                   void* stream) {
-  if (lnv_ok(L, x, dy, dres, dx, stats)) {
-    const LnvCfg v = lnv_cfg(C, B, L, true);
-    const int VNTL = (int)adp_cdiv(L, 4 * v.lpr);
-    dim3 vgrid((unsigned)VNTL, (unsigned)B);
-#define ADP_LNV_BWD(LPR, NT, VPT)                                                                                      \
-  if (v.lpr == LPR && v.nt == NT && v.vpt == VPT) {                                                                    \
-    ADP_LAUNCH((chan_lnv_bwd_kernel<LPR, NT, VPT>), vgrid, dim3(NT), stream, x, dy, ss, bstride, gamma, stats, dres,  \
-               (int)C, (int)L, VNTL, dx, ws);                                                                          \
-    return VNTL;                                                                                                       \
-  }
-    ADP_LNV_BWD(64, 256, 2) ADP_LNV_BWD(32, 256, 4) ADP_LNV_BWD(16, 256, 4) ADP_LNV_BWD(8, 256, 4) ADP_LNV_BWD(8, 1024, 2)
-    ADP_LNV_BWD(4, 1024, 2) ADP_LNV_BWD(2, 1024, 1) ADP_LNV_BWD(4, 1024, 4) ADP_LNV_BWD(2, 1024, 2) ADP_LNV_BWD(1, 1024, 1)
-    ADP_LNV_BWD(4, 512, 4) ADP_LNV_BWD(4, 512, 8) ADP_LNV_BWD(2, 512, 2) ADP_LNV_BWD(2, 512, 4) ADP_LNV_BWD(1, 512, 2) ADP_LNV_BWD(8, 512, 4)
-#undef ADP_LNV_BWD
-  }
-  const LnCfg k = ln_cfg(C, B, L);
-  const int NTL = (int)adp_cdiv(L, k.tl);
-  dim3 grid((unsigned)NTL, (unsigned)B);
-  if (k.tl == 8)
-    ADP_LAUNCH((chan_ln_bwd_kernel<8, 1024, 8>), grid, dim3(1024), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 4)
-    ADP_LAUNCH((chan_ln_bwd_kernel<4, 1024, 4>), grid, dim3(1024), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 64 && C <= 8)
-    ADP_LAUNCH((chan_ln_bwd_kernel<64, 256, 2>), grid, dim3(256), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 64 && C <= 32)
-    ADP_LAUNCH((chan_ln_bwd_kernel<64, 256, 8>), grid, dim3(256), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 64)
-    ADP_LAUNCH((chan_ln_bwd_kernel<64, 256, 16>), grid, dim3(256), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 32 && k.nt == 256)
-    ADP_LAUNCH((chan_ln_bwd_kernel<32, 256, 16>), grid, dim3(256), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else if (k.tl == 32)
-    ADP_LAUNCH((chan_ln_bwd_kernel<32, 1024, 8>), grid, dim3(1024), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  else
-    ADP_LAUNCH((chan_ln_bwd_kernel<16, 1024, 16>), grid, dim3(1024), stream, x, dy, ss, bstride, gamma, stats, dres,
-               (int)C, (int)L, NTL, dx, ws);
-  return NTL;
+  const LnPlan p = ln_plan(C, B, L, true, aligned16(x, dy, dres, dx, stats));
+  const int rc = p.vec ? ln_launch_vec<LnvBwd>(p, B, stream, x, dy, ss, bstride, gamma, stats, dres, (int)C, (int)L, p.ntl,
+                                               dx, ws)
+                       : ln_launch_row<LnBwd>(p, B, stream, x, dy, ss, bstride, gamma, stats, dres, (int)C, (int)L, p.ntl,
+                                              dx, ws);
+  return rc != ADP_OK ? rc : p.ntl;
 }
 
 // out[b*bstride + j] (or out[j] summed over b) = sum_t ws[(b*W + j)*NT + t]; one wave per row
@@ -1487,7 +1520,7 @@ extern "C" int adp_gn_stats_act(const float* x, int64_t B, int64_t C, int64_t L,
   const int64_t NG = (C / G) * L, nchunks = adp_cdiv(NG, GN_CHUNK);
   if (B * G > 65535 || B * C > 65535) return ADP_ERR_SHAPE;
   ADP_LAUNCH(gn_partial_kernel, dim3((unsigned)nchunks, (unsigned)(B * G)), dim3(256), stream, x, NG, nchunks, ws);
-  if ((L & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(act)) & 15) == 0)
+  if ((L & 3) == 0 && aligned16(x, act))
     return launch_gn_act_slab<2>(x, ws, gamma, beta, B, C, L, G, nchunks, eps, stats, act, stream);
   ADP_LAUNCH(gn_apply_kernel, dim3((unsigned)adp_cdiv(L, 1024), (unsigned)(B * C)), dim3(256), stream, x,
              (const float*)ws, gamma, beta, C, L, G, nchunks, eps, stats, act);
@@ -1501,23 +1534,11 @@ extern "C" int adp_gn_silu_bwd_reduce(const float* x, const float* dact, const f
                                       float* ab, void* stream) {
   if (!x || !dact || !stats || !gamma || !beta || !ab) return ADP_ERR_NULL;
   if (B <= 0 || C <= 0 || L <= 0 || G <= 0 || C % G || NS < 1 || NS > 65535 || B * C > 65535) return ADP_ERR_SHAPE;
-  int64_t CL = adp_cdiv(L, NS);
-  if ((L & 3) == 0) CL = (CL + 3) & ~(int64_t)3;  // (both stages derive the same segment length from L and NS)
-  if (gn_bwd_vec_ok(x, dact, nullptr, nullptr, L, CL) && (reinterpret_cast<uintptr_t>(ab) & 7) == 0) {
-    const int64_t nseg = B * C * NS;
-    const int tpr = gn_bwd_tpr(CL);
-    const dim3 grid((unsigned)adp_cdiv(nseg, 256 / tpr));
-#define ADP_GN_RED(T) \
-  ADP_LAUNCH((gn_bwd_reduce_vec_kernel<T>), grid, dim3(256), stream, x, dact, stats, gamma, beta, C, L, G, NS, CL, nseg, ab)
-    if (tpr == 16) ADP_GN_RED(16);
-    else if (tpr == 32) ADP_GN_RED(32);
-    else if (tpr == 64) ADP_GN_RED(64);
-    else ADP_GN_RED(256);
-#undef ADP_GN_RED
-    return ADP_LAUNCH_OK();
-  }
-  ADP_LAUNCH(gn_bwd_reduce_kernel, dim3((unsigned)NS, (unsigned)(B * C)), dim3(256), stream, x, dact, stats, gamma,
-             beta, C, L, G, NS, CL, ab);
+  const GnBwdPlan p = gn_bwd_plan(B, C, L, NS, x, dact, nullptr, nullptr, ab);
+  if (p.vec) {
+    ADP_GN_BWD_VEC(gn_bwd_reduce_vec_kernel, p, stream, x, dact, stats, gamma, beta, C, L, G, NS, p.CL, p.nseg, ab);
+  } else
+    ADP_LAUNCH(gn_bwd_reduce_kernel, p.grid, dim3(256), stream, x, dact, stats, gamma, beta, C, L, G, NS, p.CL, ab);
   return ADP_LAUNCH_OK();
 }
 
@@ -1527,24 +1548,13 @@ extern "C" int adp_gn_silu_bwd_apply_ab(const float* x, const float* dact, const
                                         float* dbeta, int64_t accumulate, void* stream) {
   if (!x || !dact || !stats || !gamma || !beta || !ab || !dx || (!dgamma != !dbeta)) return ADP_ERR_NULL;
   if (B <= 0 || C <= 0 || L <= 0 || G <= 0 || C % G || NS < 1 || NS > 65535 || NSab < 1 || B * C > 65535) return ADP_ERR_SHAPE;
-  int64_t CL = adp_cdiv(L, NS);
-  if ((L & 3) == 0) CL = (CL + 3) & ~(int64_t)3;
-  if (gn_bwd_vec_ok(x, dact, dres, dx, L, CL) && (reinterpret_cast<uintptr_t>(ab) & 7) == 0) {
-    const int64_t nseg = B * C * NS;
-    const int tpr = gn_bwd_tpr(CL);
-    const dim3 grid((unsigned)adp_cdiv(nseg, 256 / tpr));
-#define ADP_GN_APP(T)                                                                                                  \
-  ADP_LAUNCH((gn_bwd_apply_vec_kernel<T>), grid, dim3(256), stream, x, dact, stats, gamma, beta, ab, dres, C, L, G, NS, \
-             CL, nseg, dx, B, dgamma, dbeta, (int)accumulate, NSab)
-    if (tpr == 16) ADP_GN_APP(16);
-    else if (tpr == 32) ADP_GN_APP(32);
-    else if (tpr == 64) ADP_GN_APP(64);
-    else ADP_GN_APP(256);
-#undef ADP_GN_APP
-    return ADP_LAUNCH_OK();
-  }
-  ADP_LAUNCH(gn_bwd_apply_kernel, dim3((unsigned)NS, (unsigned)(B * C)), dim3(256), stream, x, dact, stats, gamma,
-             beta, ab, dres, C, L, G, NS, CL, dx, B, dgamma, dbeta, (int)accumulate, NSab);
+  const GnBwdPlan p = gn_bwd_plan(B, C, L, NS, x, dact, dres, dx, ab);
+  if (p.vec) {
+    ADP_GN_BWD_VEC(gn_bwd_apply_vec_kernel, p, stream, x, dact, stats, gamma, beta, ab, dres, C, L, G, NS, p.CL, p.nseg, dx, B,
+                   dgamma, dbeta, (int)accumulate, NSab);
+  } else
+    ADP_LAUNCH(gn_bwd_apply_kernel, p.grid, dim3(256), stream, x, dact, stats, gamma, beta, ab, dres, C, L, G, NS, p.CL, dx, B,
+               dgamma, dbeta, (int)accumulate, NSab);
   return ADP_LAUNCH_OK();
 }
 
@@ -1568,8 +1578,7 @@ extern "C" int adp_gn_param_grad(const float* ab, int64_t B, int64_t C, int64_t 
 extern "C" int adp_modulation_fwd(const float* x, const float* ss, int64_t ss_bstride, int64_t B, int64_t C,
                                   int64_t L, float eps, float* y, float* stats, void* stream) {
   if (!x || !ss || !y || !stats) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   return launch_ln_fwd(x, ss, ss_bstride, B, C, L, eps, y, stats, stream);
 }
 
@@ -1579,8 +1588,7 @@ extern "C" int adp_modulation_ln_fwd(const float* x, const float* ss, int64_t ss
                                      void* stream) {
   if (!x || !ss || !y || !stats || !gamma || !beta || !xn || !ln_stats) return ADP_ERR_NULL;
   if (xn2 && (!gamma2 || !beta2)) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   return launch_ln_fwd(x, ss, ss_bstride, B, C, L, eps, y, stats, stream, gamma, beta, gamma2, beta2, xn2, eps_ln, xn,
                        ln_stats);
 }
@@ -1598,7 +1606,7 @@ extern "C" int adp_gn_finalize_act(const float* x, const float* part, int64_t B,
                                    float* act, void* stream) {
   if (!x || !part || !gamma || !beta || !stats || !act) return ADP_ERR_NULL;
   if (B <= 0 || C <= 0 || L <= 0 || E <= 0 || G <= 0 || C % G || (C / G) % 4 || B * C > 65535) return ADP_ERR_SHAPE;
-  if ((L & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(act)) & 15) == 0)
+  if ((L & 3) == 0 && aligned16(x, act))
     return launch_gn_act_slab<1>(x, part, gamma, beta, B, C, L, G, E, eps, stats, act, stream);
   ADP_LAUNCH(gn_finalize_act_kernel, dim3((unsigned)adp_cdiv(L, 1024), (unsigned)(B * C)), dim3(256), stream, x, part,
              gamma, beta, C, L, G, E, eps, stats, act);
@@ -1609,7 +1617,7 @@ extern "C" int adp_gn_act(const float* x, const float* stats, const float* gamma
                           int64_t C, int64_t L, int64_t G, float* act, void* stream) {
   if (!x || !stats || !gamma || !beta || !act) return ADP_ERR_NULL;
   if (B <= 0 || C <= 0 || L <= 0 || G <= 0 || C % G || B * C > 65535) return ADP_ERR_SHAPE;
-  if ((L & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(act)) & 15) == 0)
+  if ((L & 3) == 0 && aligned16(x, act))
     return launch_gn_act_slab<0>(x, stats, gamma, beta, B, C, L, G, 0, 0.0f, (float*)nullptr, act, stream);
   ADP_LAUNCH(gn_act_kernel, dim3((unsigned)adp_cdiv(L, 1024), (unsigned)(B * C)), dim3(256), stream, x, stats, gamma,
              beta, C, L, G, act);
@@ -1618,8 +1626,7 @@ extern "C" int adp_gn_act(const float* x, const float* stats, const float* gamma
 
 extern "C" int adp_ln_stats(const float* x, int64_t B, int64_t C, int64_t L, float eps, float* stats, void* stream) {
   if (!x || !stats) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   return launch_ln_fwd(x, (const float*)nullptr, (int64_t)0, B, C, L, eps, (float*)nullptr, stats, stream);
 }
 
@@ -1628,27 +1635,26 @@ extern "C" int adp_ln_affine_fwd(const float* x, int64_t B, int64_t C, int64_t L
                                  float* stats, void* stream) {
   if (!x || !gamma || !beta || !y || !stats) return ADP_ERR_NULL;
   if (y2 && (!gamma2 || !beta2)) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   return launch_ln_fwd(x, (const float*)nullptr, (int64_t)0, B, C, L, eps, y, stats, stream, gamma, beta, gamma2, beta2,
                        y2);
 }
 
 extern "C" int64_t adp_chan_ln_bwd_ws_bytes(int64_t B, int64_t C, int64_t L) {
   if (B <= 0 || C <= 0 || L <= 0) return ADP_ERR_SHAPE;
-  // (room for whichever form the launch takes: the 16-byte form needs aligned tensors, which are not known here)
-  const int64_t t_old = adp_cdiv(L, ln_cfg(C, B, L).tl), t_vec = adp_cdiv(L, 4 * lnv_cfg(C, B, L).lpr);
-  return B * 2 * C * (t_old > t_vec ? t_old : t_vec) * (int64_t)sizeof(float);
+  // (room for whichever form the backward takes: the 16-byte form needs aligned tensors, which are not known here)
+  const int64_t t_row = ln_plan(C, B, L, true, false).ntl, t_vec = ln_plan(C, B, L, true, true).ntl;
+  return B * 2 * C * (t_row > t_vec ? t_row : t_vec) * (int64_t)sizeof(float);
 }
 
 extern "C" int adp_modulation_bwd(const float* x, const float* dy, const float* ss, int64_t ss_bstride,
                                   const float* stats, int64_t B, int64_t C, int64_t L, float* dx, float* dss,
                                   int64_t dss_bstride, float* ws, void* stream) {
   if (!x || !dy || !ss || !stats || !dx || !dss || !ws) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   const int64_t NT = launch_ln_bwd(x, dy, ss, ss_bstride, (const float*)nullptr, stats, (const float*)nullptr, B, C, L, dx,
                                    ws, stream);
+  if (NT < 0) return (int)NT;
   launch_reduce_tiles((const float*)ws, B, C, NT, dss_bstride, 0, 0, dss, stream);
   return ADP_LAUNCH_OK();
 }
@@ -1657,11 +1663,10 @@ extern "C" int64_t adp_modulation_bwd_partial(const float* x, const float* dy, c
                                               const float* stats, int64_t B, int64_t C, int64_t L, float* dx, float* ws,
                                               void* stream) {
   if (!x || !dy || !ss || !stats || !dx || !ws) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   const int64_t NT = launch_ln_bwd(x, dy, ss, ss_bstride, (const float*)nullptr, stats, (const float*)nullptr, B, C, L, dx,
                                    ws, stream);
-  return ADP_LAUNCH_OK() == ADP_OK ? NT : (int64_t)ADP_ERR_LAUNCH;
+  return NT < 0 || ADP_LAUNCH_OK() == ADP_OK ? NT : (int64_t)ADP_ERR_LAUNCH;
 }
 
 extern "C" int adp_modulation_bwd_reduce(const float* const* ws, float* const* dss, int64_t n, int64_t B, int64_t C,
@@ -1690,9 +1695,9 @@ extern "C" int adp_ln_bwd(const float* x, const float* dxn, const float* stats, 
                           int64_t B, int64_t C, int64_t L, int64_t accumulate, float* dx, float* dgamma_dbeta,
                           float* ws, void* stream) {
   if (!x || !dxn || !stats || !gamma || !dx || !dgamma_dbeta || !ws) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
   const int64_t NT = launch_ln_bwd(x, dxn, (const float*)nullptr, (int64_t)0, gamma, stats, dres, B, C, L, dx, ws, stream);
+  if (NT < 0) return (int)NT;
   // dgamma_dbeta = [dgamma (C) | dbeta (C)]
   launch_reduce_tiles((const float*)ws, B, C, NT, (int64_t)0, 1, (int)accumulate, dgamma_dbeta, stream);
   return ADP_LAUNCH_OK();
@@ -1703,31 +1708,22 @@ extern "C" int64_t adp_modulation_ln_bwd_partial(const float* x, const float* ss
                                                  const float* dres, int64_t B, int64_t C, int64_t L, int64_t accumulate,
                                                  float* dx, float* ws, float* dgamma_dbeta, float* ws_ln, void* stream) {
   if (!x || !ss || !stats || !y || !dxn || !gamma || !ln_stats || !dx || !ws || !dgamma_dbeta || !ws_ln) return ADP_ERR_NULL;
-  if (B <= 0 || C <= 0 || L <= 0 || B > 65535 || L >= (int64_t)1 << 31) return ADP_ERR_SHAPE;
-  if (C > LN_CMAX) return ADP_ERR_UNSUPPORTED;
-  int64_t NT = -1;
-  if (lnv_ok(L, x, dxn, dres, dx, stats) && lnv_ok(L, ln_stats, nullptr, nullptr, nullptr, nullptr)) {
-    const LnvCfg v = lnv_cfg(C, B, L, true);
-    const int VNTL = (int)adp_cdiv(L, 4 * v.lpr);
-    dim3 vgrid((unsigned)VNTL, (unsigned)B);
-#define ADP_LNV_CHAIN(LPR, NT_, VPT)                                                                                    \
-  if (NT < 0 && v.lpr == LPR && v.nt == NT_ && v.vpt == VPT) {                                                          \
-    ADP_LAUNCH((chan_lnv_bwd_chain_kernel<LPR, NT_, VPT>), vgrid, dim3(NT_), stream, x, ss, ss_bstride, stats, dxn,    \
-               gamma, ln_stats, dres, (int)C, (int)L, VNTL, dx, ws, ws_ln);                                             \
-    NT = VNTL;                                                                                                          \
-  }
-    ADP_LNV_CHAIN(64, 256, 2) ADP_LNV_CHAIN(32, 256, 4) ADP_LNV_CHAIN(16, 256, 4) ADP_LNV_CHAIN(8, 256, 4) ADP_LNV_CHAIN(8, 1024, 2)
-    ADP_LNV_CHAIN(4, 1024, 2) ADP_LNV_CHAIN(2, 1024, 1) ADP_LNV_CHAIN(4, 1024, 4) ADP_LNV_CHAIN(2, 1024, 2) ADP_LNV_CHAIN(1, 1024, 1)
-    ADP_LNV_CHAIN(4, 512, 4) ADP_LNV_CHAIN(4, 512, 8) ADP_LNV_CHAIN(2, 512, 2) ADP_LNV_CHAIN(2, 512, 4) ADP_LNV_CHAIN(1, 512, 2) ADP_LNV_CHAIN(8, 512, 4)
-#undef ADP_LNV_CHAIN
-    if (NT > 0) launch_reduce_tiles((const float*)ws_ln, B, C, NT, (int64_t)0, 1, (int)accumulate, dgamma_dbeta, stream);
-  }
-  if (NT < 0) {
+  if (const int rc = ln_shape_check(B, C, L)) return rc;
+  const LnPlan p = ln_plan(C, B, L, true, aligned16(x, dxn, dres, dx, stats, ln_stats));
+  int64_t NT = p.ntl;
+  if (p.vec) {
+    const int rc = ln_launch_vec<LnvBwdChain>(p, B, stream, x, ss, ss_bstride, stats, dxn, gamma, ln_stats, dres, (int)C, (int)L,
+                                              p.ntl, dx, ws, ws_ln);
+    if (rc != ADP_OK) return rc;
+    launch_reduce_tiles((const float*)ws_ln, B, C, NT, (int64_t)0, 1, (int)accumulate, dgamma_dbeta, stream);
+  } else {
     // without the 16-byte form: the two launches it stands for (d(y) passes through dx: every thread reads its own elements of
     // the incoming gradient before it writes them)
     const int64_t NA = launch_ln_bwd(y, dxn, (const float*)nullptr, (int64_t)0, gamma, ln_stats, dres, B, C, L, dx, ws_ln, stream);
+    if (NA < 0) return NA;
     launch_reduce_tiles((const float*)ws_ln, B, C, NA, (int64_t)0, 1, (int)accumulate, dgamma_dbeta, stream);
     NT = launch_ln_bwd(x, dx, ss, ss_bstride, (const float*)nullptr, stats, (const float*)nullptr, B, C, L, dx, ws, stream);
+    if (NT < 0) return NT;
   }
   return ADP_LAUNCH_OK() == ADP_OK ? NT : (int64_t)ADP_ERR_LAUNCH;
 }
