@@ -173,12 +173,21 @@ RNG_SIGNATURES = {
     "adp_v_inpaint_step_rng": (c_int, [P, P, P, P, P, P, I, P, P]),
 }
 
+# the extension header include/adp_clip.h (dynamic thresholding: per-item quantile scale, clip, thresholded sampler step),
+# one to one
+CLIP_SIGNATURES = {
+    "adp_clip_ws_bytes": (I, [I, I]),
+    "adp_clip_scale": (c_int, [P, P, P, I, I, I, F, F, P, P, P]),
+    "adp_clip_apply": (c_int, [P, P, I, I, P, P]),
+    "adp_clip_step": (c_int, [P, P, P, P, P, I, P, I, I, P, P, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
-                              **RNG_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h declare
+                              **RNG_SIGNATURES, **CLIP_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -11,6 +11,7 @@ from .diffusion import (
     VDiffusion,
     VInpainter,
     VMultistepSampler,
+    VThresholdSampler,
     VSampler,
 )
 from .losses import MultiResolutionSTFTLoss, STFTLoss
@@ -47,7 +48,7 @@ def LTPlugin(*args, **kwargs):
 
 __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
-    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "DiffusionModel",
+    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "VThresholdSampler", "DiffusionModel",
     "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
 ]

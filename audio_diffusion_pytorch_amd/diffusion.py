@@ -1,7 +1,8 @@
 """v-objective diffusion on the gfx950 kernels: `VDiffusion` (training loss) and `VSampler`
 (DDIM-style loop) and `VInpainter` (RePaint-style resampling loop), API-compatible with
 /root/reference/audio_diffusion_pytorch/diffusion.py:15-30, :62-95, :133-190, :300-354.
-`VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own.
+`VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own, and so is
+`VThresholdSampler`, which puts the reference's `clip` (dynamic thresholding, diffusion.py:36-54) inside the sampling loop.
 
 Differences from the reference are structural, not numerical:
   * noising (x_noisy, v_target) is one fused kernel (2 reads, 2 writes) instead of ~6 elementwise ops;
@@ -61,6 +62,29 @@ def alpha_beta(sigmas: Tensor) -> Tuple[Tensor, Tensor]:
     """The v-objective's (alpha, beta) = (cos, sin) of sigma * pi / 2: what every `get_alpha_beta` below returns."""
     angle = sigmas * pi / 2
     return torch.cos(angle), torch.sin(angle)
+
+
+def pad_dims(x: Tensor, ndim: int) -> Tensor:
+    """Pads `ndim` dimensions of size 1 to the right of the tensor (diffusion.py:36-38)."""
+    return x.view(*x.shape, *((1,) * ndim))
+
+
+@torch.no_grad()
+def clip(x: Tensor, dynamic_threshold: float = 0.0) -> Tensor:
+    """diffusion.py:41-54 on the kernels of include/adp_clip.h, for float32 x [B, ...], forward only.
+    dynamic_threshold == 0: clamp(x, -1, 1).  Otherwise s = max(quantile_q(|x|), 1) per batch item (torch.quantile's linear
+    rule, selected exactly without a sort) and clamp(x, -s, s) / s."""
+    if not 0.0 <= dynamic_threshold <= 1.0:
+        raise ValueError(f"clip: dynamic_threshold must be in [0, 1]; got {dynamic_threshold!r}")
+    if x.dim() < 1:
+        raise ValueError("clip: x must be [B, ...]")
+    with _on_device_of(x):
+        x = x.contiguous()
+        if dynamic_threshold == 0.0:
+            scale = torch.ones(x.shape[0], dtype=torch.float32, device=x.device)  # (x / 1 is exact)
+        else:
+            scale = ops.clip_scale(x, dynamic_threshold, min_scale=1.0)
+        return ops.clip_apply(x, scale)
 
 
 """ Diffusion """
@@ -269,6 +293,10 @@ class VSampler(_CapturedSteps, Sampler):
         written).  The one piece a subclass replaces: everything around it in forward / _forward_graph is shared."""
         return ops.v_step(x, v, row, out=out)
 
+    def _step_key(self) -> Tuple:
+        """What of this sampler's configuration a captured step depends on beyond the call structure (part of the cache key)."""
+        return ()
+
     HOIST_MAX_BYTES = 512 << 20  # cap of the hoisted conditioning table (README net: 360 KB per step and batch element)
 
     def _conditioning_table(self, sig: Tensor, num_steps: int, b: int, kwargs) -> Optional[Tensor]:
@@ -339,7 +367,7 @@ class VSampler(_CapturedSteps, Sampler):
 
             return sx, step, dict(ssig=ssig, sab=sab, scond=scond, bufs=bufs)
 
-        entry = self._captured_step(x, kwargs, build, (cond is not None,))
+        entry = self._captured_step(x, kwargs, build, (cond is not None,) + tuple(self._step_key()))
         if entry is None:
             return None
         self.graph_replays += 1
@@ -407,6 +435,61 @@ class VMultistepSampler(VSampler):
             return super()._step(x, v, row, bufs, out)
         hist_x0, hist_eps = bufs
         return ops.v_step2(x, v, hist_x0, hist_eps, row, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
+
+
+class VThresholdSampler(VMultistepSampler):
+    """`VSampler` (order=1) or `VMultistepSampler` (order=2) with the predicted clean signal thresholded at every step: what
+    keeps a bounded signal (audio in [-1, 1]) bounded under classifier-free guidance, where x0 = a x - b v leaves the range at
+    the noisy end of the schedule.  Not in the reference, whose `clip` (diffusion.py:41-54) has no caller.
+
+        x0  = a_i x - b_i v            eps = b_i x + a_i v
+        x0c = clip(x0, dynamic_threshold)
+        order 1:  x_{i+1} = a_{i+1} x0c + b_{i+1} eps
+        order 2:  x_{i+1} = a_{i+1} x0c + b_{i+1} eps + ca_i (x0c - x0c_{i-1}) + cb_i (eps - eps_{i-1})
+
+    eps is kept from the RAW prediction, the usual form of thresholded DDIM: re-deriving it from the clipped x0 would divide by
+    b_i, which goes to 0 at the clean end of the schedule.  The second-order history holds the clipped x0.
+
+    `dynamic_threshold=q` > 0: per batch item s = max(quantile_q(|x0|), 1), x0c = clamp(x0, -s, s) / s -- an exact order
+    statistic by a three-pass radix select over the bits of |x0| (include/adp_clip.h), five small launches in front of the
+    update kernel, no sort and no host read, so the whole step still replays from one hipGraph.  `dynamic_threshold=0.0` is
+    the static clamp to [-1, 1]: the update kernel alone.  The scale row, the select's workspace and the history are step
+    buffers: a captured step owns its own, and (threshold, order) are part of its cache key."""
+
+    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), dynamic_threshold: float = 0.995,
+                 order: int = 1, use_graph: bool = True):
+        if order not in (1, 2):
+            raise ValueError(f"VThresholdSampler: order must be 1 or 2; got {order!r}")
+        if isinstance(dynamic_threshold, bool) or not isinstance(dynamic_threshold, (int, float)) \
+                or not 0.0 <= dynamic_threshold <= 1.0:
+            raise ValueError(f"VThresholdSampler: dynamic_threshold must be a number in [0, 1]; got {dynamic_threshold!r}")
+        super().__init__(net=net, schedule=schedule, order=order, use_graph=use_graph)
+        self.dynamic_threshold = float(dynamic_threshold)
+
+    def _tables(self, num_steps: int, b: int, device):
+        """`VMultistepSampler`'s tables: rows of 4 coefficients for order 1, of 6 for order 2."""
+        return super()._tables(num_steps, b, device)
+
+    def _step_key(self) -> Tuple:
+        return (float(self.dynamic_threshold), self.order)
+
+    def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
+        """(scale [B], select workspace) when the threshold is dynamic, then `VMultistepSampler`'s history.  All left
+        uninitialised: every step zeroes the workspace it uses and writes the scale before reading it."""
+        hist = super()._step_buffers(x)
+        if self.dynamic_threshold == 0.0:
+            return hist
+        return (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x)) + tuple(hist)
+
+    def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
+        scale, hist = None, bufs
+        if len(bufs) > (0 if self.order == 1 else 2):  # the dynamic threshold's buffers lead the history
+            scale, ws, hist = bufs[0], bufs[1], bufs[2:]
+            ops.clip_scale(x, self.dynamic_threshold, v=v, coef=row, min_scale=1.0, ws=ws, out=scale)
+        if self.order == 1:
+            return ops.clip_step(x, v, row, scale, out=out)
+        hist_x0, hist_eps = hist
+        return ops.clip_step(x, v, row, scale, hist_x0, hist_eps, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
 
 
 """ Inpainters """

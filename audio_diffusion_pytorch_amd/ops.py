@@ -8,7 +8,7 @@ import contextlib
 import ctypes
 import os
 from ctypes import byref
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -755,6 +755,116 @@ def v_inpaint_step_rng(x: Tensor, v: Tensor, source: Tensor, mask_u8: Tensor, ab
     _C.call("adp_v_inpaint_step_rng", ptr(x), ptr(v), ptr(source), ptr(mask_u8, torch.uint8), ptr(ab4), row, x.numel(),
             ptr(out), _C.stream())
     return out
+
+
+# ---- include/adp_clip.h: dynamic thresholding (per-item quantile scale, clip, thresholded sampler step)
+
+CLIP_MAX_PER = 1 << 24  # per - 1 is exact in float32 up to here (torch.quantile's own limit)
+
+
+def _clip_dims(what: str, x) -> Tuple[int, int]:
+    """(rows, per) of a [B, ...] batch, from its shape alone (nothing is read or launched before the checks pass)."""
+    shape = tuple(int(s) for s in x.shape)
+    if len(shape) < 1:
+        raise ValueError(f"{what}: x must be [B, ...]; got a scalar")
+    rows, per = shape[0], 1
+    for s in shape[1:]:
+        per *= s
+    if per > CLIP_MAX_PER:
+        raise ValueError(f"{what}: {per} values per item; the quantile is defined for at most 2**24 = {CLIP_MAX_PER}")
+    return rows, per
+
+
+def clip_rank(q: float, per: int) -> Tuple[int, float]:
+    """(lo, w) of torch.quantile's linear rule, in its float32 arithmetic: rank = float32(q) * float32(per - 1)."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"clip_rank: q must be in [0, 1]; got {q!r}")
+    if not 1 <= per <= CLIP_MAX_PER:
+        raise ValueError(f"clip_rank: per must be in [1, 2**24]; got {per}")
+    rank = torch.tensor(float(q), dtype=torch.float32) * torch.tensor(float(per - 1), dtype=torch.float32)
+    lo = torch.floor(rank)
+    return int(lo.item()), float((rank - lo).item())
+
+
+def clip_ws(x: Tensor) -> Tensor:
+    """The workspace `clip_scale` needs for x [B, ...] (uninitialised: the call zeroes what it uses)."""
+    rows, per = _clip_dims("clip_ws", x)
+    return _ws(_C.query("adp_clip_ws_bytes", rows, per), x)
+
+
+def clip_scale(x: Tensor, q: float, v: Optional[Tensor] = None, coef: Optional[Tensor] = None, min_scale: float = 1.0,
+               ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """scale [B] = max(quantile_q(|y|), min_scale) per item of x [B, ...] (adp_clip_scale), y = x, or coef[0] x - coef[1] v
+    when v is given (coef: device row whose first two values are a0, b0).  torch.quantile's linear rule, exact selection,
+    no sort, no host read; a row holding a NaN gets NaN."""
+    rows, per = _clip_dims("clip_scale", x)
+    if (v is None) != (coef is None):
+        raise ValueError("clip_scale: v and coef go together")
+    if v is not None and v.shape != x.shape:
+        raise ValueError(f"clip_scale: v must have x's shape {tuple(x.shape)}; got {tuple(v.shape)}")
+    if coef is not None and coef.numel() < 2:
+        raise ValueError(f"clip_scale: coef holds (a0, b0, ...); got {coef.numel()} values")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=x.device)
+    elif out.numel() != rows:
+        raise ValueError(f"clip_scale: out must hold {rows} values; got {out.numel()}")
+    if rows == 0 or per == 0:
+        return out
+    lo, w = clip_rank(q, per)
+    need = _C.query("adp_clip_ws_bytes", rows, per)
+    if ws is None:
+        ws = _ws(need, x)
+    elif ws.numel() * ws.element_size() < need:
+        raise ValueError(f"clip_scale: the workspace holds {ws.numel() * ws.element_size()} bytes; {need} needed")
+    _C.call("adp_clip_scale", ptr(x), ptr(v), ptr(coef), rows, per, lo, w, float(min_scale), ptr(ws, ws.dtype), ptr(out),
+            _C.stream())
+    return out
+
+
+def clip_apply(x: Tensor, scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """clamp(x, -s, s) / s with one s per item of x [B, ...] (adp_clip_apply).  `out` may be x."""
+    rows, per = _clip_dims("clip_apply", x)
+    if scale.numel() != rows:
+        raise ValueError(f"clip_apply: scale must hold one value per item ({rows}); got {scale.numel()}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise ValueError(f"clip_apply: out must have x's shape {tuple(x.shape)}; got {tuple(out.shape)}")
+    _C.call("adp_clip_apply", ptr(x), ptr(scale), rows, per, ptr(out), _C.stream())
+    return out
+
+
+def clip_step(x: Tensor, v: Tensor, coef: Tensor, scale: Optional[Tensor] = None, hist_x0: Optional[Tensor] = None,
+              hist_eps: Optional[Tensor] = None, out: Optional[Tensor] = None, hist_x0_out: Optional[Tensor] = None,
+              hist_eps_out: Optional[Tensor] = None):
+    """One thresholded v-sampler update (adp_clip_step) on x [B, ...]: the predicted x0 is clamped to the item's scale and
+    divided by it (scale=None: clamped to [-1, 1]); eps comes from the raw v.  A coef row of 4 values is the first-order
+    step and returns x_next; one of 6 values (a0, b0, a1, b1, ca, cb) the second-order step on the history and returns
+    (x_next, clipped x0, eps).  Every output may be its input; a row with ca = cb = 0 does not read the history."""
+    rows, per = _clip_dims("clip_step", x)
+    if coef.numel() not in (4, 6):
+        raise ValueError(f"clip_step: coef holds (a0, b0, a1, b1) or (a0, b0, a1, b1, ca, cb); got {coef.numel()} values")
+    order = 1 if coef.numel() == 4 else 2
+    for t in (v, hist_x0, hist_eps, out, hist_x0_out, hist_eps_out):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"clip_step: every tensor must have x's shape {tuple(x.shape)}; got {tuple(t.shape)}")
+    if scale is not None and scale.numel() != rows:
+        raise ValueError(f"clip_step: scale must hold one value per item ({rows}); got {scale.numel()}")
+    if out is None:
+        out = torch.empty_like(x)
+    if order == 1:
+        if hist_x0 is not None or hist_eps is not None or hist_x0_out is not None or hist_eps_out is not None:
+            raise ValueError("clip_step: the first-order step (4 coefficients) has no history")
+    else:
+        if hist_x0 is None or hist_eps is None:
+            raise ValueError("clip_step: the second-order step (6 coefficients) needs hist_x0 and hist_eps")
+        if hist_x0_out is None:
+            hist_x0_out = torch.empty_like(x)
+        if hist_eps_out is None:
+            hist_eps_out = torch.empty_like(x)
+    _C.call("adp_clip_step", ptr(x), ptr(v), ptr(hist_x0), ptr(hist_eps), ptr(coef), order, ptr(scale), rows, per, ptr(out),
+            ptr(hist_x0_out), ptr(hist_eps_out), _C.stream())
+    return out if order == 1 else (out, hist_x0_out, hist_eps_out)
 
 
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:

@@ -1,0 +1,168 @@
+"""The entry points of include/adp_clip.h with misaligned operands and guard bands (tests/placement.py), as
+tests/test_rng_placement.py does for include/adp_rng.h: every operand of a direct call through `_C.lib()` is placed by the test
+at the zero / all1 / mixed / single1 / single2 placements.  A placed call returns ADP_OK, gives the values of the restatement
+(tests/test_threshold_sampler.py: the quantile of |x| within 2**-22 relative, the fused one within its derived bound, the
+elementwise kernels within their roundings) and leaves every guard, offset gap and input payload bit-identical.  Two items per
+call; two lengths: one on the 16-byte paths (which a misplaced pointer must leave) and an odd one, whose second item starts
+off the 16-byte grid wherever the first one is."""
+import os
+import re
+
+import pytest
+import torch
+
+from audio_diffusion_pytorch_amd import _C
+from conftest import rel_err
+from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from test_multistep_sampler import KERNEL_TOL, coef_table
+from test_threshold_sampler import CLIP_TOL, LERP_TOL, clip_ref, quantile_ref, rank_of, threshold_step_ref
+
+ROWS, Q = 2, 0.9
+LENGTHS = {"vec": 2048, "odd": 1001}
+COEF = coef_table(torch.tensor([0.62, 0.55, 0.5]))[1].to(torch.float32)   # (a0, b0, a1, b1, ca, cb), ca and cb not 0
+
+
+def _data(n, count):
+    g = torch.Generator().manual_seed(n)
+    return [torch.randn(ROWS, n, generator=g) * 1.5 for _ in range(count)]
+
+
+def _ws_numel(n):
+    return (_C.query("adp_clip_ws_bytes", ROWS, n) + 3) // 4
+
+
+def _scale(P, n):
+    (x,) = _data(n, 1)
+    xd = P.inp("x", x)
+    ws, out = P.ws("ws", _ws_numel(n)), P.out("scale", (ROWS,))
+    lo, _, w = rank_of(Q, n)
+    code = _C.lib().adp_clip_scale(p(xd), None, None, ROWS, n, lo, float(w), 0.0, p(ws), p(out), _C.stream())
+    want = torch.quantile(x.abs(), Q, dim=-1)
+    return code, lambda: [("scale", ((out.cpu() - want).abs() / want).max().item(), LERP_TOL)]
+
+
+def _scale_fused(P, n):
+    x, v = _data(n, 2)
+    xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef", COEF)
+    ws, out = P.ws("ws", _ws_numel(n)), P.out("scale", (ROWS,))
+    lo, _, w = rank_of(Q, n)
+    code = _C.lib().adp_clip_scale(p(xd), p(vd), p(cd), ROWS, n, lo, float(w), 1.0, p(ws), p(out), _C.stream())
+    a0, b0 = COEF[0].double(), COEF[1].double()
+    want = quantile_ref((a0 * x.double() - b0 * v.double()).abs(), Q).clamp(min=1.0)
+    bound = 4 * 2.0 ** -24 * ((a0 * x.double()).abs() + (b0 * v.double()).abs()).max().item()
+    return code, lambda: [("scale", (out.cpu().double() - want).abs().max().item(), bound)]
+
+
+def _apply(P, n):
+    (x,) = _data(n, 1)
+    scale = torch.tensor([1.0, 1.75])
+    xd, sd = P.inp("x", x), P.inp("scale", scale)
+    out = P.out("out", (ROWS, n))
+    code = _C.lib().adp_clip_apply(p(xd), p(sd), ROWS, n, p(out), _C.stream())
+    want = x.clamp(-scale[:, None], scale[:, None]) / scale[:, None]
+    return code, lambda: [("out", rel_err(out, want), CLIP_TOL)]
+
+
+def _step(order, dynamic):
+    def run(P, n):
+        x, v, hx, he = _data(n, 4)
+        scale = torch.tensor([1.0, 1.75])
+        row = COEF if order == 2 else COEF[:4].contiguous()
+        xd, vd = P.inp("x", x), P.inp("v", v)
+        hxd = hed = None
+        if order == 2:
+            hxd, hed = P.inp("hist_x0", hx), P.inp("hist_eps", he)
+        cd = P.inp("coef", row)
+        sd = P.inp("scale", scale) if dynamic else None
+        outs = [P.out("x_out", (ROWS, n))]
+        if order == 2:
+            outs += [P.out("hist_x0_out", (ROWS, n)), P.out("hist_eps_out", (ROWS, n))]
+        code = _C.lib().adp_clip_step(p(xd), p(vd), p(hxd), p(hed), p(cd), order, p(sd), ROWS, n, p(outs[0]),
+                                      p(outs[1]) if order == 2 else None, p(outs[2]) if order == 2 else None, _C.stream())
+        want = threshold_step_ref(x, v, hx, he, row, scale if dynamic else None)
+        return code, lambda: [(name, rel_err(o, r), KERNEL_TOL)
+                              for name, o, r in zip(("x_out", "hist_x0_out", "hist_eps_out"), outs, want)]
+    return run
+
+
+CASES = {"scale": (_scale, "adp_clip_scale"), "scale_fused": (_scale_fused, "adp_clip_scale"),
+         "apply": (_apply, "adp_clip_apply"), "step1": (_step(1, True), "adp_clip_step"),
+         "step2": (_step(2, True), "adp_clip_step"), "step2_static": (_step(2, False), "adp_clip_step")}
+HOST_ONLY = {"adp_clip_ws_bytes"}   # takes no pointer
+
+
+def place_and_check(dev, name, length, plan, what):
+    fn, entry = CASES[name]
+    P = Placer(dev, plan)
+    code, figures = fn(P, LENGTHS[length])
+    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
+    problems = []
+    for label, err, bound in figures():
+        print(f"{entry} ({name}) {length} [{what}] {label}: {err:.3e} (bound {bound:.3e})")
+        if not err <= bound:
+            problems.append(f"{label}: {err:.3e} > {bound:.3e}")
+    P.arena.verify()   # raises PlacementError naming the operand and the span
+    assert not problems, f"{entry} ({name}) {length}, placement {what}:\n" + "\n".join(problems)
+    return P
+
+
+@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
+@pytest.mark.parametrize("length", list(LENGTHS))
+@pytest.mark.parametrize("name", list(CASES))
+def test_whole_call_placements(dev, name, length, kind):
+    place_and_check(dev, name, length, PLANS[kind], kind)
+
+
+@pytest.mark.parametrize("length", list(LENGTHS))
+@pytest.mark.parametrize("name", list(CASES))
+def test_single_operand_placements(dev, name, length):
+    """single1: each pointer operand alone at offset 1; single2: each output alone at offset 2 (the 8-byte phase)."""
+    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
+    for operand, role in base.operands:
+        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
+        if role in OUTPUT_ROLES:
+            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+
+
+def test_placement_does_not_change_the_values(dev):
+    """The selection is exact and the arithmetic per element: the 16-byte and the single-element paths agree bit for bit."""
+    outs = []
+    for kind in ("zero", "all1"):
+        P = Placer(dev, PLANS[kind])
+        x, v = _data(LENGTHS["vec"], 2)
+        xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef", COEF)
+        ws, scale = P.ws("ws", _ws_numel(LENGTHS["vec"])), P.out("scale", (ROWS,))
+        lo, _, w = rank_of(Q, LENGTHS["vec"])
+        assert _C.lib().adp_clip_scale(p(xd), p(vd), p(cd), ROWS, LENGTHS["vec"], lo, float(w), 1.0, p(ws), p(scale),
+                                       _C.stream()) == 0
+        out = P.out("x_out", (ROWS, LENGTHS["vec"]))
+        assert _C.lib().adp_clip_step(p(xd), p(vd), None, None, p(cd), 1, p(scale), ROWS, LENGTHS["vec"], p(out), None, None,
+                                      _C.stream()) == 0
+        outs.append((scale.cpu().clone(), out.cpu().clone()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+def test_every_clip_entry_point_is_placed():
+    assert {entry for _, entry in CASES.values()} | HOST_ONLY == set(_C.CLIP_SIGNATURES)
+    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES, _C.RNG_SIGNATURES):
+        assert not set(_C.CLIP_SIGNATURES) & set(other)
+
+
+def test_header_table_and_libraries_agree(emul):
+    """include/adp_clip.h <-> _C.CLIP_SIGNATURES <-> what the built libraries export."""
+    import ctypes
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "adp_clip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
+    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
+    assert declared == set(_C.CLIP_SIGNATURES), declared ^ set(_C.CLIP_SIGNATURES)
+    for name in declared:
+        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
+    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
+    hip_lib = ctypes.CDLL(_C.LIB_PATH)
+    for name in declared:
+        assert hasattr(hip_lib, name), name
+    source = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "clip.hip")).read()
+    assert '#include "adp_clip.h"' in source
+    # one helper forms x0 for the select's passes and for the step: they must round alike
+    assert source.count("clip_x0(") >= 3 and "__fmaf_rn" in source
