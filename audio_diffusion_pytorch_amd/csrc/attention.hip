@@ -19,6 +19,7 @@
 // The dk/dv pass splits the QUERY range over several waves when there are few key tiles (cross attention: m = 64
 // keys x n = 4096 queries) and sums the partial tiles in a second, deterministic stage.  D <= 64, multiple of 2.
 #include <stdlib.h>
+#include <algorithm>
 #include "adp_rt.h"
 #include "adp.h"
 
@@ -917,17 +918,6 @@ __global__ __launch_bounds__(256) void attn_bwd_fewkeys_kernel(attn_fk_args a) {
   }
 }
 
-// query split of the key-major pass: enough waves to cover the chip when there are few key tiles
-int64_t kv_nsplit(int64_t B, int64_t H, int64_t n, int64_t m) {
-  const int64_t ktiles = (m + 31) / 32, qtiles = (n + 31) / 32;
-  int64_t ns = 1024 / (B * H * ktiles);          // target ~1024 waves (4 per CU),
-  if (ns > qtiles) ns = qtiles;                  // down to one query tile per wave (a wave is serial: 8 us per tile; the
-                                                 // old floor of four tiles left n = 256 cross attention on 32 waves)
-  if (ns > 32) ns = 32;                          // and a bounded number of partial copies to sum
-  if (ns < 1) ns = 1;
-  return ns;
-}
-
 // key split of the query-major passes (forward, dq): when B * H * query tiles leaves most SIMDs idle (batch 1: 256 waves
 // at n = 1024, 32 at n = 128) the key range is cut into up to 8 slices run by separate waves
 int64_t q_nsplit(int64_t B, int64_t H, int64_t n, int64_t m, int64_t* tps_out) {
@@ -946,161 +936,171 @@ bool attn_shape_ok(int64_t B, int64_t H, int64_t D, int64_t n, int64_t m) {
          D * n < ((int64_t)1 << 31) && D * m < ((int64_t)1 << 31);  // 32-bit element offsets inside one head's slab
 }
 
+// The host half: one plan per direction decides the form, the splits and the workspace, and the entry points ask it.  The knobs
+// are read in the plans and nowhere else, on every call (the tests flip them inside one process).
+enum AttnForm { ATTN_TILED, ATTN_FEWKEYS, ATTN_MERGED, ATTN_SPLIT };  // forward: tiled or few-keys; backward: the last three
+struct AttnFwdPlan {
+  int rc;             // ADP_OK, or what the entry points refuse
+  AttnForm form;
+  int64_t ns, tps;    // key split of the tiled form: slices, key tiles per slice
+  int64_t ws_floats;  // ns > 1: ns partial copies of o [B, H, D, n] and of its two softmax statistics [B, H, n]
+};
+
+AttnFwdPlan attn_fwd_plan(int64_t B, int64_t H, int64_t D, int64_t n, int64_t m, bool have_ws) {
+  AttnFwdPlan p = {ADP_OK, ATTN_TILED, 1, adp_cdiv(m, 32), 0};
+  if (!attn_shape_ok(B, H, D, n, m)) return p.rc = ADP_ERR_SHAPE, p;
+  if (have_ws) p.ns = q_nsplit(B, H, n, m, &p.tps);  // (a call without a workspace runs unsplit)
+  // few keys (cross attention over the embedding): four waves per query tile (ADP_ATTN_FEWKEYS=0: the one-wave form, A/B).
+  // It has no split form and needs none: q_nsplit keeps two key tiles per slice, so m <= 64 always has ns == 1
+  if (D == 64 && m <= 64 && p.ns == 1 && adp_knob_on("ADP_ATTN_FEWKEYS")) p.form = ATTN_FEWKEYS;
+  if (p.ns > 1) p.ws_floats = p.ns * B * H * (D * n + 2 * n);
+  return p;
+}
+
+// The backward workspace, in floats, one region after the other (a region is empty when its split is 1):
+//   delta [B, H, n] | ns partial copies of dk | ns partial copies of dv | nq partial copies of dq
+// One partial copy is addressed exactly like the result it is summed into: pstride = B * kv_bstride, qstride = B * q_bstride.
+struct AttnBwdPlan {
+  int rc;                    // ADP_OK, or what the entry points refuse
+  AttnForm form;
+  int64_t ns, tps;           // query split of the key-major pass: slices, query tiles per slice
+  int64_t nq, qtps;          // key split of the query-major pass: slices, key tiles per slice
+  int64_t ns4, tps4;         // few-keys form: the query split of its key-major role
+  int64_t gq, gkv;           // merged and split forms: workgroups of the query-major / key-major pass
+  int64_t pstride, qstride;  // 0 when the pass is not split
+  int64_t delta_off, dk_off, dv_off, dq_off, ws_floats;
+};
+
+// INVARIANT (it makes adp_attn_bwd_ws_bytes, which knows no strides, a safe size; adp_attn_bwd checks it): the plan at any accepted
+// strides needs no more floats than the plan at packed strides (q_bstride = H*D*n; kv_bstride = 2*H*D*m, k and v being the halves of
+// one projection output): the dk | dv partials are refused for a larger kv_bstride and the dq partials exist only for packed q.
+AttnBwdPlan attn_bwd_plan(int64_t B, int64_t H, int64_t D, int64_t n, int64_t m, int64_t q_bstride, int64_t kv_bstride) {
+  AttnBwdPlan p = {};
+  if (!attn_shape_ok(B, H, D, n, m)) return p.rc = ADP_ERR_SHAPE, p;
+  const int64_t ktiles = adp_cdiv(m, 32), qtiles = adp_cdiv(n, 32);
+  // query split of the key-major pass: enough waves to cover the chip when there are few key tiles
+  p.ns = 1024 / (B * H * ktiles);        // target ~1024 waves (4 per CU),
+  if (p.ns > qtiles) p.ns = qtiles;      // down to one query tile per wave (a wave is serial: 8 us per tile; the old floor of
+                                         // four tiles left n = 256 cross attention on 32 waves)
+  if (p.ns > 32) p.ns = 32;              // and a bounded number of partial copies to sum
+  if (p.ns < 1) p.ns = 1;
+  p.tps = adp_cdiv(qtiles, p.ns);
+  if (p.ns > 1 && kv_bstride > 2 * H * D * m) return p.rc = ADP_ERR_UNSUPPORTED, p;  // (before any form is considered)
+  p.nq = 1, p.qtps = ktiles;
+  if (q_bstride == H * D * n) p.nq = q_nsplit(B, H, n, m, &p.qtps);  // key split of the query-major pass: packed q only
+  p.pstride = p.ns > 1 ? B * kv_bstride : 0, p.qstride = p.nq > 1 ? B * q_bstride : 0;
+  p.dk_off = p.delta_off + B * H * n;
+  p.dv_off = p.dk_off + p.ns * p.pstride;
+  p.dq_off = p.dv_off + p.ns * p.pstride;
+  p.ws_floats = p.dq_off + p.nq * p.qstride;
+  p.gq = adp_cdiv(n, 128) * p.nq, p.gkv = adp_cdiv(ktiles * p.ns, 4);
+  // few keys: four waves per query tile / per query slice in one launch (ADP_ATTN_FEWKEYS=0: the one-wave forms, A/B)
+  // (taken while the query tiles are few: at 1024+ the chip is full of one-wave items either way -- hipGraph microbench, us per
+  // backward, one-wave forms -> this kernel: batch 1 n = 128 16.4 -> 9.8, 256 16.2 -> 9.5, 1024 20.9 -> 17.0, 4096 52.1 ->
+  // 51.3; batch 4 n = 256 20.0 -> 15.9, n = 1024 40.4 -> 45.6, n = 4096 123 -> 177)
+  if (D == 64 && m <= 64 && B * H * qtiles <= (B * H <= 8 ? 1024 : 512) && adp_knob_on("ADP_ATTN_FEWKEYS")) {
+    p.form = ATTN_FEWKEYS;
+    // ~two workgroups per CU for the key-major role, at most 32 copies to sum, and no more than the dk | dv regions hold (ns >= 1)
+    p.ns4 = std::max<int64_t>(1, std::min({adp_knob("ADP_ATTN_FK_SLICES", 512) / (B * H), qtiles, (int64_t)32, p.ns}));
+    p.tps4 = adp_cdiv(qtiles, p.ns4);
+    p.ns4 = adp_cdiv(qtiles, p.tps4);  // every slice non-empty
+    return p;
+  }
+  // One launch for both passes while together they are at most one wave per SIMD (batch 1; hipGraph microbench, us per backward,
+  // separate -> merged: cross attention over 64 keys n = 128 27.6 -> 16.6, n = 1024 32.3 -> 20.7, n = 4096 (1536 waves) 52.3 ->
+  // 53.1; self attention n = 256 35.1 -> 21.7, n = 1024 (2048 waves: the chip is full either way and the key-major pass pays
+  // for its O columns) 107 -> 127).  ADP_ATTN_MERGE=0 / 1 forces either form (tests, A/B).
+  p.form = adp_knob_on("ADP_ATTN_MERGE", (p.gq + p.gkv) * H * B * 4 <= 1024) ? ATTN_MERGED : ATTN_SPLIT;
+  return p;
+}
+
+// KERNEL<true> for 64 channels per head, KERNEL<false> otherwise
+#define ATTN_LAUNCH_D64(KERNEL, grid, ...)                                                 \
+  do {                                                                                     \
+    if (D == 64) ADP_LAUNCH(KERNEL<true>, grid, dim3(256), stream, __VA_ARGS__);           \
+    else ADP_LAUNCH(KERNEL<false>, grid, dim3(256), stream, __VA_ARGS__);                  \
+  } while (0)
+
 }  // namespace
 
 extern "C" int64_t adp_attn_fwd_ws_bytes(int64_t B, int64_t H, int64_t D, int64_t n, int64_t m) {
-  if (!attn_shape_ok(B, H, D, n, m)) return ADP_ERR_SHAPE;
-  int64_t tps;
-  const int64_t ns = q_nsplit(B, H, n, m, &tps);
-  return ns > 1 ? ns * B * H * (D * n + 2 * n) * (int64_t)sizeof(float) : 0;
+  const AttnFwdPlan p = attn_fwd_plan(B, H, D, n, m, true);
+  return p.rc != ADP_OK ? p.rc : p.ws_floats * (int64_t)sizeof(float);
 }
 
 extern "C" int adp_attn_fwd(const float* q, const float* k, const float* v, int64_t B, int64_t H, int64_t D,
                             int64_t n, int64_t m, int64_t q_bstride, int64_t kv_bstride, float* o, float* lse,
                             float* ws, void* stream) {
   if (!q || !k || !v || !o || !lse) return ADP_ERR_NULL;
-  if (!attn_shape_ok(B, H, D, n, m)) return ADP_ERR_SHAPE;
+  const AttnFwdPlan p = attn_fwd_plan(B, H, D, n, m, ws != nullptr);
+  if (p.rc != ADP_OK) return p.rc;
   const float scale = 1.0f / sqrtf((float)D);
-  int64_t tps = adp_cdiv(m, 32);
-  const int64_t ns = ws ? q_nsplit(B, H, n, m, &tps) : 1;
-  if (ns == 1) tps = adp_cdiv(m, 32);
-  {  // few keys (cross attention over the embedding): four waves per query tile (ADP_ATTN_FEWKEYS=0: the one-wave form, A/B)
-    if (D == 64 && m <= 64 && ns == 1 && adp_knob_on("ADP_ATTN_FEWKEYS")) {
-      ADP_LAUNCH(attn_fwd_fewkeys_kernel, dim3((unsigned)adp_cdiv(n, 32), (unsigned)H, (unsigned)B), dim3(256), stream, q, k, v,
-                 (int)H, (int)n, (int)m, q_bstride, kv_bstride, scale, o, lse);
-      return ADP_LAUNCH_OK();
-    }
+  if (p.form == ATTN_FEWKEYS) {
+    ADP_LAUNCH(attn_fwd_fewkeys_kernel, dim3((unsigned)adp_cdiv(n, 32), (unsigned)H, (unsigned)B), dim3(256), stream, q, k, v,
+               (int)H, (int)n, (int)m, q_bstride, kv_bstride, scale, o, lse);
+    return ADP_LAUNCH_OK();
   }
-  const dim3 grid((unsigned)(adp_cdiv(n, 128) * ns), (unsigned)H, (unsigned)B);
-  if (D == 64)
-    ADP_LAUNCH(attn_fwd_kernel<true>, grid, dim3(256), stream, q, k, v, (int)H, (int)D, (int)n, (int)m, q_bstride,
-               kv_bstride, scale, o, lse, (int)ns, (int)tps, ws);
-  else
-    ADP_LAUNCH(attn_fwd_kernel<false>, grid, dim3(256), stream, q, k, v, (int)H, (int)D, (int)n, (int)m, q_bstride,
-               kv_bstride, scale, o, lse, (int)ns, (int)tps, ws);
-  if (ns > 1)
+  ATTN_LAUNCH_D64(attn_fwd_kernel, dim3((unsigned)(adp_cdiv(n, 128) * p.ns), (unsigned)H, (unsigned)B), q, k, v, (int)H, (int)D,
+                  (int)n, (int)m, q_bstride, kv_bstride, scale, o, lse, (int)p.ns, (int)p.tps, ws);
+  if (p.ns > 1)
     ADP_LAUNCH(attn_fwd_combine_kernel, dim3((unsigned)adp_cdiv(n, 64), (unsigned)(B * H), (unsigned)adp_cdiv(D, 4)), dim3(256), stream,
-               (const float*)ws, (int)ns, (int)D, n, B * H, o, lse);
+               (const float*)ws, (int)p.ns, (int)D, n, B * H, o, lse);
   return ADP_LAUNCH_OK();
 }
 
 extern "C" int64_t adp_attn_bwd_ws_bytes(int64_t B, int64_t H, int64_t D, int64_t n, int64_t m) {
-  if (!attn_shape_ok(B, H, D, n, m)) return ADP_ERR_SHAPE;
-  const int64_t ns = kv_nsplit(B, H, n, m);
-  int64_t tps;
-  const int64_t nq = q_nsplit(B, H, n, m, &tps);
-  // delta [B, H, n] + (query-split dk/dv pass) nsplit partial copies of dk and of dv, each B * kv_bstride floats at
-  // most 2*H*D*m per batch element (k and v are the two halves of one projection output) + (key-split dq pass) nq
-  // partial copies of dq (packed q: q_bstride = H*D*n)
-  return (B * H * n + (ns > 1 ? 2 * ns * B * 2 * H * D * m : 0) + (nq > 1 ? nq * B * H * D * n : 0)) * (int64_t)sizeof(float);
+  const AttnBwdPlan p = attn_bwd_plan(B, H, D, n, m, H * D * n, 2 * H * D * m);
+  return p.rc != ADP_OK ? p.rc : p.ws_floats * (int64_t)sizeof(float);
 }
 
-extern "C" int adp_attn_bwd(const float* q, const float* k, const float* v, const float* o, const float* dout,
-                            const float* lse, int64_t B, int64_t H, int64_t D, int64_t n, int64_t m,
-                            int64_t q_bstride, int64_t kv_bstride, float* dq, float* dk, float* dv, float* ws,
-                            void* stream) {
+extern "C" int adp_attn_bwd(const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse,
+                            int64_t B, int64_t H, int64_t D, int64_t n, int64_t m, int64_t q_bstride, int64_t kv_bstride,
+                            float* dq, float* dk, float* dv, float* ws, void* stream) {
   if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !ws) return ADP_ERR_NULL;
-  if (!attn_shape_ok(B, H, D, n, m)) return ADP_ERR_SHAPE;
+  const AttnBwdPlan p = attn_bwd_plan(B, H, D, n, m, q_bstride, kv_bstride);
+  if (p.rc != ADP_OK) return p.rc;
+  if (p.ws_floats * (int64_t)sizeof(float) > adp_attn_bwd_ws_bytes(B, H, D, n, m)) return ADP_ERR_UNSUPPORTED;  // (the invariant)
   const float scale = 1.0f / sqrtf((float)D);
-  const int64_t ns = kv_nsplit(B, H, n, m), ktiles = adp_cdiv(m, 32), qtiles = adp_cdiv(n, 32);
-  const int64_t tps = adp_cdiv(qtiles, ns);  // query tiles per split
-  float* pk = dk;
-  float* pv = dv;
-  int64_t pstride = 0;
-  if (ns > 1) {
-    if (kv_bstride > 2 * H * D * m) return ADP_ERR_UNSUPPORTED;  // the partial copies are sized for packed k|v
-    pstride = B * kv_bstride;                 // one partial copy, addressed exactly like dk / dv
-    pk = ws + B * H * n;
-    pv = pk + ns * pstride;
-  }
-  // query-major pass first: it also computes delta = rowsum(dO * O) for its queries and leaves it in ws[0 .. B*H*n) for the
-  // key-major pass.  Key-split when the query tiles alone do not fill the chip (needs packed q: one partial copy is
-  // addressed exactly like dq)
-  int64_t qtps = ktiles;
-  int64_t nq = (q_bstride == H * D * n) ? q_nsplit(B, H, n, m, &qtps) : 1;
-  if (nq == 1) qtps = ktiles;
-  float* pq = dq;
-  int64_t qstride = 0;
-  if (nq > 1) {
-    pq = ws + B * H * n + (ns > 1 ? 2 * ns * pstride : 0);
-    qstride = B * q_bstride;
-  }
-  {  // few keys: four waves per query tile / per query slice in one launch (ADP_ATTN_FEWKEYS=0: the one-wave forms, A/B)
-    // (taken while the query tiles are few: at 1024+ the chip is full of one-wave items either way -- hipGraph microbench, us per
-    // backward, one-wave forms -> this kernel: batch 1 n = 128 16.4 -> 9.8, 256 16.2 -> 9.5, 1024 20.9 -> 17.0, 4096 52.1 ->
-    // 51.3; batch 4 n = 256 20.0 -> 15.9, n = 1024 40.4 -> 45.6, n = 4096 123 -> 177)
-    if (D == 64 && m <= 64 && B * H * qtiles <= (B * H <= 8 ? 1024 : 512) && adp_knob_on("ADP_ATTN_FEWKEYS")) {
-      int64_t ns4 = adp_knob("ADP_ATTN_FK_SLICES", 512) / (B * H);  // ~two workgroups per CU for the key-major role
-      if (ns4 > qtiles) ns4 = qtiles;
-      if (ns4 > 32) ns4 = 32;
-      if (ns4 < 1) ns4 = 1;
-      if (ns4 > ns) ns4 = ns;  // (the scratch is sized for kv_nsplit partial copies)
-      const int64_t tps4 = adp_cdiv(qtiles, ns4);
-      ns4 = adp_cdiv(qtiles, tps4);  // every slice non-empty
+  float* delta = ws + p.delta_off;  // rowsum(dO * O): the query-major pass leaves it for the key-major pass
+  float* pk = p.ns > 1 ? ws + p.dk_off : dk;
+  float* pv = p.ns > 1 ? ws + p.dv_off : dv;
+  float* pq = p.nq > 1 ? ws + p.dq_off : dq;
+  const int64_t qcnt = H * D * n, kvcnt = H * D * m;  // dq is an [H*D, n] slab, dk and dv [H*D, m] slabs, inside each batch stride
+  const dim3 gq2((unsigned)p.gq, (unsigned)H, (unsigned)B), gkv((unsigned)p.gkv, (unsigned)H, (unsigned)B);
+  if (p.form != ATTN_SPLIT) {  // one launch that computes its own delta, then one that sums whatever was split
+    const int64_t nsr = p.form == ATTN_FEWKEYS ? p.ns4 : p.ns;
+    if (p.form == ATTN_FEWKEYS) {
       attn_fk_args a;
       a.q = q, a.k = k, a.v = v, a.o = o, a.dout = dout, a.lse = lse;
       a.H = (int)H, a.n = (int)n, a.m = (int)m, a.qbs = q_bstride, a.kvbs = kv_bstride, a.scale = scale;
-      a.dq = dq;
-      a.dk = ns4 > 1 ? pk : dk, a.dv = ns4 > 1 ? pv : dv;
-      a.ns = (int)ns4, a.tps = (int)tps4, a.pstride = pstride, a.gq = (int)qtiles;
-      unsigned gx4 = (unsigned)(qtiles + ns4);
-#ifdef ADP_ATTN_FK_DEBUG
-      if (const char* eo = adp_knob_raw("ADP_ATTN_FK_ONLY")) {  // timing only (results incomplete): one role alone
-        if (eo[0] == 'q') gx4 = (unsigned)qtiles;
-        if (eo[0] == 'k') a.gq = 0, gx4 = (unsigned)ns4;
-      }
-#endif
-      ADP_LAUNCH(attn_bwd_fewkeys_kernel, dim3(gx4, (unsigned)H, (unsigned)B), dim3(256), stream, a);
-      if (ns4 > 1) {
-        const int64_t gx = adp_cdiv(H * D * m, 256);
-        ADP_LAUNCH(attn_bwd_reduce_kernel, dim3((unsigned)(gx < 2048 ? gx : 2048), (unsigned)(2 * B)), dim3(256), stream,
-                   (const float*)dq, 1, (int64_t)0, q_bstride, H * D * n, dq, 0, (const float*)pk, (const float*)pv, (int)ns4,
-                   pstride, kv_bstride, H * D * m, dk, dv);
-      }
-      return ADP_LAUNCH_OK();
+      a.dq = dq, a.dk = nsr > 1 ? pk : dk, a.dv = nsr > 1 ? pv : dv;
+      a.ns = (int)nsr, a.tps = (int)p.tps4, a.pstride = p.pstride, a.gq = (int)adp_cdiv(n, 32);
+      ADP_LAUNCH(attn_bwd_fewkeys_kernel, dim3((unsigned)(a.gq + nsr), (unsigned)H, (unsigned)B), dim3(256), stream, a);
+    } else {
+      attn_bwd_args a;
+      a.q = q, a.k = k, a.v = v, a.o = o, a.dout = dout, a.lse = lse;
+      a.H = (int)H, a.D = (int)D, a.n = (int)n, a.m = (int)m, a.qbs = q_bstride, a.kvbs = kv_bstride, a.scale = scale;
+      a.dq = pq, a.qtps = (int)p.qtps, a.qstride = p.qstride;
+      a.dk = pk, a.dv = pv, a.ns = (int)nsr, a.tps = (int)p.tps, a.pstride = p.pstride, a.gq = (int)gq2.x;
+      ATTN_LAUNCH_D64(attn_bwd_merged_kernel, dim3(gq2.x + gkv.x, (unsigned)H, (unsigned)B), a);
     }
-  }
-  const dim3 gq2((unsigned)(adp_cdiv(n, 128) * nq), (unsigned)H, (unsigned)B);
-  const dim3 gkv((unsigned)adp_cdiv(ktiles * ns, 4), (unsigned)H, (unsigned)B);
-  // One launch for both passes while together they are at most one wave per SIMD (batch 1; hipGraph microbench, us per backward,
-  // separate -> merged: cross attention over 64 keys n = 128 27.6 -> 16.6, n = 1024 32.3 -> 20.7, n = 4096 (1536 waves) 52.3 ->
-  // 53.1; self attention n = 256 35.1 -> 21.7, n = 1024 (2048 waves: the chip is full either way and the key-major pass pays
-  // for its O columns) 107 -> 127).  ADP_ATTN_MERGE=0 / 1 forces either form (tests, A/B).
-  const bool merge = adp_knob_on("ADP_ATTN_MERGE", (int64_t)(gq2.x + gkv.x) * H * B * 4 <= 1024);
-  if (merge) {
-    attn_bwd_args a;
-    a.q = q, a.k = k, a.v = v, a.o = o, a.dout = dout, a.lse = lse;
-    a.H = (int)H, a.D = (int)D, a.n = (int)n, a.m = (int)m, a.qbs = q_bstride, a.kvbs = kv_bstride, a.scale = scale;
-    a.dq = pq, a.qtps = (int)qtps, a.qstride = qstride;
-    a.dk = pk, a.dv = pv, a.ns = (int)ns, a.tps = (int)tps, a.pstride = pstride, a.gq = (int)gq2.x;
-    const dim3 grid(gq2.x + gkv.x, (unsigned)H, (unsigned)B);
-    if (D == 64) ADP_LAUNCH(attn_bwd_merged_kernel<true>, grid, dim3(256), stream, a);
-    else ADP_LAUNCH(attn_bwd_merged_kernel<false>, grid, dim3(256), stream, a);
-    if (nq > 1 || ns > 1) {
-      const int64_t gx = nq > 1 ? adp_cdiv(H * D * n, 256) : adp_cdiv(H * D * m, 256);
-      const dim3 gr((unsigned)(gx < 2048 ? gx : 2048), (unsigned)((nq > 1 ? B : 0) + (ns > 1 ? 2 * B : 0)));
-      ADP_LAUNCH(attn_bwd_reduce_kernel, gr, dim3(256), stream, (const float*)pq, (int)nq, qstride, q_bstride, H * D * n, dq,
-                 (int)(nq > 1 ? B : 0), (const float*)pk, (const float*)pv, (int)ns, pstride, kv_bstride, H * D * m, dk, dv);
+    if (p.nq > 1 || nsr > 1) {  // (few keys: nq == 1, pq == dq)
+      const int64_t gx = adp_cdiv(p.nq > 1 ? qcnt : kvcnt, 256);
+      const dim3 gr((unsigned)(gx < 2048 ? gx : 2048), (unsigned)((p.nq > 1 ? B : 0) + (nsr > 1 ? 2 * B : 0)));
+      ADP_LAUNCH(attn_bwd_reduce_kernel, gr, dim3(256), stream, (const float*)pq, (int)p.nq, p.qstride, q_bstride, qcnt, dq,
+                 (int)(p.nq > 1 ? B : 0), (const float*)pk, (const float*)pv, (int)nsr, p.pstride, kv_bstride, kvcnt, dk, dv);
     }
     return ADP_LAUNCH_OK();
   }
-  if (D == 64)
-    ADP_LAUNCH(attn_bwd_q_kernel<true>, gq2, dim3(256), stream, q, k, v, o, dout, lse, ws, (int)H, (int)D, (int)n, (int)m,
-               q_bstride, kv_bstride, scale, pq, (int)qtps, qstride);
-  else
-    ADP_LAUNCH(attn_bwd_q_kernel<false>, gq2, dim3(256), stream, q, k, v, o, dout, lse, ws, (int)H, (int)D, (int)n, (int)m,
-               q_bstride, kv_bstride, scale, pq, (int)qtps, qstride);
-  if (nq > 1)
-    ADP_LAUNCH(attn_sum_splits_kernel, dim3((unsigned)adp_cdiv(H * D * n, 256), (unsigned)B), dim3(256), stream,
-               (const float*)pq, (int)nq, qstride, q_bstride, H * D * n, dq);
-  if (D == 64)
-    ADP_LAUNCH(attn_bwd_kv_kernel<true>, gkv, dim3(256), stream, q, k, v, dout, lse, (const float*)ws, (int)H, (int)D,
-               (int)n, (int)m, q_bstride, kv_bstride, scale, (int)ns, (int)tps, pstride, pk, pv);
-  else
-    ADP_LAUNCH(attn_bwd_kv_kernel<false>, gkv, dim3(256), stream, q, k, v, dout, lse, (const float*)ws, (int)H, (int)D,
-               (int)n, (int)m, q_bstride, kv_bstride, scale, (int)ns, (int)tps, pstride, pk, pv);
-  if (ns > 1)  // dk and dv are [H*D, m] slabs inside each batch stride
-    ADP_LAUNCH(attn_kv_reduce_kernel, dim3((unsigned)adp_cdiv(H * D * m, 256), (unsigned)(2 * B)), dim3(256), stream,
-               (const float*)pk, (const float*)pv, (int)ns, pstride, kv_bstride, H * D * m, dk, dv);
+  ATTN_LAUNCH_D64(attn_bwd_q_kernel, gq2, q, k, v, o, dout, lse, delta, (int)H, (int)D, (int)n, (int)m, q_bstride, kv_bstride,
+                  scale, pq, (int)p.qtps, p.qstride);
+  if (p.nq > 1)
+    ADP_LAUNCH(attn_sum_splits_kernel, dim3((unsigned)adp_cdiv(qcnt, 256), (unsigned)B), dim3(256), stream, (const float*)pq,
+               (int)p.nq, p.qstride, q_bstride, qcnt, dq);
+  ATTN_LAUNCH_D64(attn_bwd_kv_kernel, gkv, q, k, v, dout, lse, (const float*)delta, (int)H, (int)D, (int)n, (int)m, q_bstride,
+                  kv_bstride, scale, (int)p.ns, (int)p.tps, p.pstride, pk, pv);
+  if (p.ns > 1)
+    ADP_LAUNCH(attn_kv_reduce_kernel, dim3((unsigned)adp_cdiv(kvcnt, 256), (unsigned)(2 * B)), dim3(256), stream,
+               (const float*)pk, (const float*)pv, (int)p.ns, p.pstride, kv_bstride, kvcnt, dk, dv);
   return ADP_LAUNCH_OK();
 }
