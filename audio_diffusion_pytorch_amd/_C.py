@@ -183,11 +183,18 @@ CLIP_SIGNATURES = {
 }
 
 
+# the extension header include/adp_gated.h (the gated feed-forward GEMM of the T5 v1.1 / flan-T5 encoder), one to one
+GATED_SIGNATURES = {
+    "adp_gated_linear_ws_bytes": (I, [I, I, I]),
+    "adp_gated_linear": (c_int, [P, P, P, I, I, I, I, P, P, P]),
+}
+
+
 def _bind(path: str):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
-                              **RNG_SIGNATURES, **CLIP_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h declare
+                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

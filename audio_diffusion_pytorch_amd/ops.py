@@ -1133,6 +1133,33 @@ def t5_attn(qkv: Tensor, rel_table: Tensor, bucket: Tensor, mask_u8: Optional[Te
     return out
 
 
+# ---- gated feed-forward GEMM of the T5 v1.1 / flan-T5 encoder (include/adp_gated.h); forward only
+GATED_ACT_GELU_NEW = 1
+
+
+def gated_linear_ws_bytes(T: int, K: int, F: int) -> int:
+    return _C.query("adp_gated_linear_ws_bytes", T, K, F)
+
+
+def gated_linear(x: Tensor, w_gate: Tensor, w_up: Tensor, out: Optional[Tensor] = None,
+                 ws: Optional[Tensor] = None) -> Tensor:
+    """gelu_new(x [T, K] @ w_gate [F, K]^T) * (x @ w_up [F, K]^T) -> [T, F] in one GEMM (adp_gated_linear); `out` overlaps
+    no input.  `ws`: at least gated_linear_ws_bytes(T, K, F) bytes, allocated here when not given."""
+    T, K = x.shape
+    F = w_gate.shape[0]
+    assert w_gate.shape == (F, K) and w_up.shape == (F, K), "gated_linear: both weights are [out, in]"
+    if out is None:
+        out = _lt_out((T, F), x)
+    nbytes = gated_linear_ws_bytes(T, K, F)
+    if ws is None and nbytes:
+        ws = _ws(nbytes, x)
+    assert nbytes == 0 or ws.numel() * 4 >= nbytes, "gated_linear: workspace too small"
+    _C.tag(flops=4 * T * K * F, bytes=4 * (T * K + 2 * F * K + T * F), shape=f"T{T} K{K} F{F}")
+    _C.call("adp_gated_linear", ptr(x), ptr(w_gate), ptr(w_up), T, K, F, GATED_ACT_GELU_NEW, ptr(out),
+            ptr(ws) if nbytes else None, _C.stream())
+    return out
+
+
 def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(a)

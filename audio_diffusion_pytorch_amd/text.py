@@ -1,18 +1,22 @@
-"""The frozen T5 text encoder on the kernels of include/adp_t5.h, and the embedder that feeds it to the U-Net:
+"""The frozen T5 text encoders on the kernels of include/adp_t5.h and include/adp_gated.h, and the embedder that feeds them
+to the U-Net:
 
+    encoder = load_t5_encoder("google/flan-t5-base")          # T5Encoder or T5GatedEncoder, by the local config
     encoder = T5Encoder.from_pretrained("t5-base")            # or T5Encoder(...) + load_hf_state_dict(sd)
     net = UNetV0(..., use_text_conditioning=True, text_embedder=T5Embedder(encoder, tokenizer))
     net(x, t, text=["a dog barking", ...])
 
 `components.T5Embedder` (the stock `transformers` model, the default when no `text_embedder` is given) is unchanged.  The
-encoder here is T5's encoder stack as `transformers.T5EncoderModel` computes it in eval mode (tests/t5_ref.py restates it and
-is checked against transformers): the original T5 layout with the ReLU feed-forward; the gated-GELU feed-forward of T5 v1.1 /
-flan-T5 is not built.  Forward only: every parameter is frozen and no kernel has a gradient.
+encoders here are T5's encoder stack as `transformers.T5EncoderModel` computes it in eval mode (tests/t5_ref.py and
+tests/t5_gated_ref.py restate it and are checked against transformers): `T5Encoder` is the original T5 layout with the ReLU
+feed-forward (t5-small/base/large), `T5GatedEncoder` the T5 v1.1 / flan-T5 layout with the gated-GELU feed-forward
+h + wo(gelu_new(a wi_0^T) * (a wi_1^T)).  Forward only: every parameter is frozen and no kernel has a gradient.
 
 Launches per encode: 1 embed, per block [rmsnorm, ONE q/k/v GEMM on the [3 H dk, d] weight packed at load time, attention,
-output GEMM + residual, rmsnorm, wi GEMM + ReLU, wo GEMM + residual], 1 final rmsnorm; a GEMM whose k sum is cut (ops.t5_linear)
-is two kernels.  No host synchronisation; after one eager call per sequence length (which uploads that length's bucket table)
-the forward can be captured into a hipGraph.
+output GEMM + residual, rmsnorm, wi GEMM + ReLU (gated: ONE gated GEMM on the [2, d_ff, d] weight pair, ops.gated_linear),
+wo GEMM + residual], 1 final rmsnorm; a GEMM whose k sum is cut (ops.t5_linear, ops.gated_linear) is two kernels.  No host
+synchronisation; after one eager call per sequence length (which uploads that length's bucket table) the forward can be
+captured into a hipGraph.
 """
 import math
 from typing import List, Optional
@@ -53,15 +57,20 @@ def _missing_weights(model: str) -> str:
 
 class T5Encoder(nn.Module):
     """input_ids int64 [B, m], attention_mask [B, m] or None -> last hidden state [B, m, d_model]."""
+    FEED_FORWARD = "relu"   # the feed_forward_proj this class computes
+
+    @staticmethod
+    def _refusal(feed_forward_proj: str) -> str:
+        return (f"T5Encoder: feed_forward_proj={feed_forward_proj!r} is not built here; T5Encoder covers the original T5 "
+                "layout (t5-small/base/large: 'relu'), and the gated feed-forward of T5 v1.1 / flan-T5 ('gated-gelu') is "
+                "text.T5GatedEncoder (text.load_t5_encoder picks the class from the local config)")
 
     def __init__(self, vocab_size: int, d_model: int, d_kv: int, d_ff: int, num_layers: int, num_heads: int,
                  relative_attention_num_buckets: int = 32, relative_attention_max_distance: int = 128,
                  layer_norm_epsilon: float = 1e-6, feed_forward_proj: str = "relu"):
         super().__init__()
-        if feed_forward_proj != "relu":
-            raise NotImplementedError(
-                f"T5Encoder: feed_forward_proj={feed_forward_proj!r} (the gated feed-forward of T5 v1.1 / flan-T5) is not "
-                "built; the native encoder covers the original T5 layout (t5-small/base/large: 'relu')")
+        if feed_forward_proj != self.FEED_FORWARD:
+            raise NotImplementedError(self._refusal(feed_forward_proj))
         if d_kv % 8 or not 8 <= d_kv <= 128:
             raise NotImplementedError(f"T5Encoder: d_kv must be a multiple of 8 in [8, 128] (adp_t5_attn); got {d_kv}")
         if relative_attention_num_buckets < 4:
@@ -81,11 +90,26 @@ class T5Encoder(nn.Module):
         self.w_qkv = frozen(L, 3 * inner, d_model, std=d_model ** -0.5)              # rows: q | k | v, head major
         self.w_o = frozen(L, d_model, inner, std=inner ** -0.5)
         self.ln_ff = frozen(L, d_model)
-        self.w_i = frozen(L, d_ff, d_model, std=d_model ** -0.5)
+        self._init_wi(frozen)
         self.w_o2 = frozen(L, d_model, d_ff, std=d_ff ** -0.5)
         self.ln_final = frozen(d_model)
         self._buckets = {}   # (m, device) -> int32 [2m - 1] on that device
         self._ws_bytes = {}  # T -> workspace bytes of the largest GEMM
+
+    # ---- the feed-forward's first half: what T5GatedEncoder replaces
+    def _init_wi(self, frozen) -> None:
+        self.w_i = frozen(self.num_layers, self.d_ff, self.d_model, std=self.d_model ** -0.5)
+
+    def _get_wi(self, get, ff: str) -> Tensor:
+        """Block `ff`'s slice of w_i from a state dict (`get(key, shape)` checks and converts)."""
+        return get(ff + "DenseReluDense.wi.weight", (self.d_ff, self.d_model))
+
+    def _wi_ws_bytes(self, T: int) -> int:
+        return ops.t5_linear_ws_bytes(T, self.d_model, self.d_ff)
+
+    def _wi(self, n: int, a: Tensor, f: Tensor, ws: Optional[Tensor]) -> None:
+        """f [T, d_ff] = block n's activation of the normed tokens a [T, d]: one launch (two where the k sum is cut)."""
+        ops.t5_linear(a, self.w_i[n], relu=True, out=f, ws=ws)
 
     # ---- weights
     def load_hf_state_dict(self, sd) -> None:
@@ -101,7 +125,7 @@ class T5Encoder(nn.Module):
                 raise KeyError(key)
             t = sd[key]
             if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"T5Encoder.load_hf_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+                raise ValueError(f"{type(self).__name__}.load_hf_state_dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
             return t.detach().to(dtype=torch.float32)
 
         staged = {"embed": get("shared.weight", (self.vocab_size, d)),
@@ -115,7 +139,7 @@ class T5Encoder(nn.Module):
             per["w_qkv"].append(torch.cat([get(att + f"SelfAttention.{p}.weight", (inner, d)) for p in "qkv"], dim=0))
             per["w_o"].append(get(att + "SelfAttention.o.weight", (d, inner)))
             per["ln_ff"].append(get(ff + "layer_norm.weight", (d,)))
-            per["w_i"].append(get(ff + "DenseReluDense.wi.weight", (self.d_ff, d)))
+            per["w_i"].append(self._get_wi(get, ff))
             per["w_o2"].append(get(ff + "DenseReluDense.wo.weight", (d, self.d_ff)))
         staged.update({k: torch.stack(v) for k, v in per.items()})
         with torch.no_grad():   # nothing is written before every key and shape has passed
@@ -131,11 +155,16 @@ class T5Encoder(nn.Module):
             sd = T5EncoderModel.from_pretrained(name_or_path, local_files_only=True).state_dict()
         except Exception as e:
             raise NotImplementedError(_missing_weights(name_or_path)) from e
+        cls._check_config(cfg)
         enc = cls(cfg.vocab_size, cfg.d_model, cfg.d_kv, cfg.d_ff, cfg.num_layers, cfg.num_heads,
                   cfg.relative_attention_num_buckets, getattr(cfg, "relative_attention_max_distance", 128),
                   cfg.layer_norm_epsilon, cfg.feed_forward_proj)
         enc.load_hf_state_dict(sd)
         return enc
+
+    @classmethod
+    def _check_config(cls, cfg) -> None:
+        """Refuses a local config whose feed-forward this class does not compute (here: left to the constructor)."""
 
     # ---- forward
     def _bucket(self, m: int, device) -> Tensor:
@@ -147,7 +176,8 @@ class T5Encoder(nn.Module):
     def _workspace(self, T: int, like: Tensor) -> Optional[Tensor]:
         if T not in self._ws_bytes:
             inner, d, f = self.num_heads * self.d_kv, self.d_model, self.d_ff
-            self._ws_bytes[T] = max(ops.t5_linear_ws_bytes(T, K, N) for K, N in ((d, 3 * inner), (inner, d), (d, f), (f, d)))
+            self._ws_bytes[T] = max([ops.t5_linear_ws_bytes(T, K, N) for K, N in ((d, 3 * inner), (inner, d), (f, d))]
+                                    + [self._wi_ws_bytes(T)])
         n = self._ws_bytes[T]
         return torch.empty(n // 4, dtype=torch.float32, device=like.device) if n else None
 
@@ -177,9 +207,60 @@ class T5Encoder(nn.Module):
             ops.t5_attn(qkv.view(B, m, 3 * inner), self.rel_bias, bucket, mask, H, out=o.view(B, m, inner))
             ops.t5_linear(o, self.w_o[n], res=h, out=h, ws=ws)
             ops.t5_rmsnorm(h, self.ln_ff[n], self.eps, out=a)
-            ops.t5_linear(a, self.w_i[n], relu=True, out=f, ws=ws)
+            self._wi(n, a, f, ws)
             ops.t5_linear(f, self.w_o2[n], res=h, out=h, ws=ws)
         return ops.t5_rmsnorm(h, self.ln_final, self.eps).view(B, m, d)
+
+
+class T5GatedEncoder(T5Encoder):
+    """The T5 v1.1 / flan-T5 encoder: T5Encoder with the gated-GELU feed-forward h + wo(gelu_new(a wi_0^T) * (a wi_1^T)).
+    Constructor arguments are T5Encoder's with feed_forward_proj="gated-gelu".  Both first-half weights of a stack live in
+    ONE frozen parameter w_i [L, 2, d_ff, d] (0: wi_0, the gate, which goes through the activation; 1: wi_1, the up
+    projection), whose two contiguous slices are the two weight pointers of ops.gated_linear: one GEMM stages the normed
+    tokens once, forms both products and applies the gate, so a block launches what a ReLU block launches."""
+    FEED_FORWARD = "gated-gelu"
+
+    def __init__(self, vocab_size: int, d_model: int, d_kv: int, d_ff: int, num_layers: int, num_heads: int,
+                 relative_attention_num_buckets: int = 32, relative_attention_max_distance: int = 128,
+                 layer_norm_epsilon: float = 1e-6, feed_forward_proj: str = "gated-gelu"):
+        super().__init__(vocab_size, d_model, d_kv, d_ff, num_layers, num_heads, relative_attention_num_buckets,
+                         relative_attention_max_distance, layer_norm_epsilon, feed_forward_proj)
+
+    @staticmethod
+    def _refusal(feed_forward_proj: str) -> str:
+        return (f"T5GatedEncoder: feed_forward_proj={feed_forward_proj!r} is not built; T5GatedEncoder covers 'gated-gelu' "
+                "(gelu_new gate: T5 v1.1, flan-T5), text.T5Encoder covers 'relu'; gated-silu and ungated gelu are not built")
+
+    def _init_wi(self, frozen) -> None:
+        self.w_i = frozen(self.num_layers, 2, self.d_ff, self.d_model, std=self.d_model ** -0.5)
+
+    def _get_wi(self, get, ff: str) -> Tensor:
+        return torch.stack([get(ff + f"DenseReluDense.wi_{i}.weight", (self.d_ff, self.d_model)) for i in (0, 1)])
+
+    def _wi_ws_bytes(self, T: int) -> int:
+        return ops.gated_linear_ws_bytes(T, self.d_model, self.d_ff)
+
+    def _wi(self, n: int, a: Tensor, f: Tensor, ws: Optional[Tensor]) -> None:
+        ops.gated_linear(a, self.w_i[n, 0], self.w_i[n, 1], out=f, ws=ws)
+
+    @classmethod
+    def _check_config(cls, cfg) -> None:
+        if not getattr(cfg, "is_gated_act", False) or getattr(cfg, "dense_act_fn", None) != "gelu_new":
+            raise NotImplementedError(cls._refusal(getattr(cfg, "feed_forward_proj", None)))
+
+
+def load_t5_encoder(name_or_path: str) -> T5Encoder:
+    """The native encoder of a local T5 checkpoint (`transformers`' local files only; never downloads): a T5Encoder where
+    its config says feed_forward_proj 'relu', a T5GatedEncoder where it says 'gated-gelu'."""
+    try:
+        from transformers import AutoConfig
+        cfg = AutoConfig.from_pretrained(name_or_path, local_files_only=True)
+    except Exception as e:
+        raise NotImplementedError(_missing_weights(name_or_path)) from e
+    for cls in (T5Encoder, T5GatedEncoder):
+        if getattr(cfg, "feed_forward_proj", None) == cls.FEED_FORWARD:
+            return cls.from_pretrained(name_or_path)
+    raise NotImplementedError(T5GatedEncoder._refusal(getattr(cfg, "feed_forward_proj", None)))
 
 
 class T5Embedder(nn.Module):
@@ -187,7 +268,7 @@ class T5Embedder(nn.Module):
     encoder.  `tokenizer(texts, truncation=True, max_length=..., padding="max_length", return_tensors="pt")` returns
     `input_ids` and `attention_mask` -- a HuggingFace tokenizer, or any callable of that shape."""
 
-    def __init__(self, encoder: T5Encoder, tokenizer, max_length: int = 64):
+    def __init__(self, encoder: T5Encoder, tokenizer, max_length: int = 64):   # (a T5GatedEncoder is a T5Encoder)
         super().__init__()
         self.encoder, self.tokenizer, self.max_length = encoder, tokenizer, max_length
 

@@ -1,7 +1,11 @@
-"""One text encode on the GPU at t5-base's geometry (vocab 32128, d_model 768, 12 heads of 64, d_ff 3072, 12 blocks, random
-weights), m = 64 tokens, B = 1 and B = 4.  Subjects, timed in one process and interleaved repeat by repeat:
+"""One text encode on the GPU, random weights, m = 64 tokens, B = 1 and B = 4, at the geometry --ff names:
 
-    native_eager   text.T5Encoder, one Python call per kernel launch
+    relu         t5-base       vocab 32128, d_model 768, 12 heads of 64, d_ff 3072, 12 blocks    text.T5Encoder
+    gated-gelu   flan-t5-base  vocab 32128, d_model 768, 12 heads of 64, d_ff 2048, 12 blocks    text.T5GatedEncoder
+
+Subjects, timed in one process and interleaved repeat by repeat:
+
+    native_eager   the native encoder, one Python call per kernel launch
     native_graph   the same forward captured once and replayed from a hipGraph
     torch_eager    transformers.T5EncoderModel with the SAME weights on the same GPU (library GEMMs); only where
                    transformers is importable -- what a user has without the native encoder
@@ -10,7 +14,8 @@ Medians over --reps repeats with the min-max spread; launches per encode (native
 bytes an encode must stream over the replayed time as GB/s); then ONE profiled native pass per batch size (a HIP event pair
 per launch) for the per-kernel split.  Writes one JSON object to --out and prints it.  The measurement runs in a child
 process under --timeout seconds; this process never opens the GPU.
-usage: python tools/t5_bench.py [--reps R] [--inner I] [--timeout S] [--out profiles/t5_bench.json]"""
+--out holds one object per --ff: a run replaces its own entry and keeps the other.
+usage: python tools/t5_bench.py [--ff relu|gated-gelu] [--reps R] [--inner I] [--timeout S] [--out profiles/t5_bench.json]"""
 import argparse
 import json
 import os
@@ -19,7 +24,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GEOM = dict(vocab_size=32128, d_model=768, d_kv=64, d_ff=3072, num_layers=12, num_heads=12)
+GEOMS = {"relu": dict(vocab_size=32128, d_model=768, d_kv=64, d_ff=3072, num_layers=12, num_heads=12),
+         "gated-gelu": dict(vocab_size=32128, d_model=768, d_kv=64, d_ff=2048, num_layers=12, num_heads=12)}
 TOKENS = 64
 
 
@@ -27,16 +33,18 @@ def worker(args):
     import torch
     sys.path.insert(0, ROOT)
     from audio_diffusion_pytorch_amd import _C
-    from audio_diffusion_pytorch_amd.text import T5Encoder
+    from audio_diffusion_pytorch_amd.text import T5Encoder, T5GatedEncoder
 
+    GEOM = GEOMS[args.ff]
+    Encoder = {"relu": T5Encoder, "gated-gelu": T5GatedEncoder}[args.ff]
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    enc = T5Encoder(**GEOM).to(dev)
+    enc = Encoder(**GEOM).to(dev)
     hf = None
     try:
         import transformers
-        hf = transformers.T5EncoderModel(transformers.T5Config(**GEOM, feed_forward_proj="relu", dropout_rate=0.0)).eval()
-        enc_cpu = T5Encoder(**GEOM)
+        hf = transformers.T5EncoderModel(transformers.T5Config(**GEOM, feed_forward_proj=args.ff, dropout_rate=0.0)).eval()
+        enc_cpu = Encoder(**GEOM)
         enc_cpu.load_hf_state_dict(hf.state_dict())   # the same weights on both sides
         enc = enc_cpu.to(dev)
         hf = hf.to(dev)
@@ -44,8 +52,9 @@ def worker(args):
         pass
     inner = GEOM["num_heads"] * GEOM["d_kv"]
     # what an encode must read once: every block's matrices (the embedding rows and norm weights are noise next to them)
-    weight_bytes = 4 * GEOM["num_layers"] * (4 * inner * GEOM["d_model"] + 2 * GEOM["d_model"] * GEOM["d_ff"])
-    res = {"geometry": GEOM, "tokens": TOKENS, "reps": args.reps, "inner": args.inner, "weight_bytes": weight_bytes,
+    ff_mats = 3 if args.ff == "gated-gelu" else 2
+    weight_bytes = 4 * GEOM["num_layers"] * (4 * inner * GEOM["d_model"] + ff_mats * GEOM["d_model"] * GEOM["d_ff"])
+    res = {"feed_forward_proj": args.ff, "geometry": GEOM, "tokens": TOKENS, "reps": args.reps, "inner": args.inner, "weight_bytes": weight_bytes,
            "transformers": None if hf is None else transformers.__version__, "batches": {}}
     for B in (1, 4):
         g = torch.Generator().manual_seed(B)
@@ -117,15 +126,21 @@ def worker(args):
                                        for k, v in sorted(split.items(), key=lambda kv: -kv[1]["ms"])}
         r["native_kernel_sum_ms"] = round(total, 4)
         res["batches"][f"B{B}"] = r
-    text = json.dumps(res)
+    both = {}
+    if os.path.exists(args.out):   # one entry per --ff; a file of the earlier single-object layout is a ReLU run
+        with open(args.out) as f:
+            old = json.load(f)
+        both = {"relu": old} if "batches" in old else old
+    both[args.ff] = res
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text, flush=True)
+        f.write(json.dumps(both) + "\n")
+    print(json.dumps(res), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ff", choices=sorted(GEOMS), default="relu", help="the feed-forward, and with it the geometry")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=420)
@@ -134,7 +149,7 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(args)
-    cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--reps", str(args.reps), "--inner", str(args.inner),
+    cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--ff", args.ff, "--reps", str(args.reps), "--inner", str(args.inner),
            "--out", args.out]
     try:
         sys.exit(subprocess.run(cmd, timeout=args.timeout).returncode)
