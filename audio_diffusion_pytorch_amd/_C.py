@@ -189,12 +189,17 @@ GATED_SIGNATURES = {
     "adp_gated_linear": (c_int, [P, P, P, I, I, I, I, P, P, P]),
 }
 
+# the extension header include/adp_sde.h (the stochastic v-sampler step on in-register Philox noise), one to one
+SDE_SIGNATURES = {
+    "adp_v_step_eta": (c_int, [P, P, P, P, I, P, I, I, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
-                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h declare
+                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES, **SDE_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h / adp_sde.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -12,6 +12,7 @@ from .diffusion import (
     VInpainter,
     VMultistepSampler,
     VThresholdSampler,
+    VStochasticSampler,
     VSampler,
 )
 from .losses import MultiResolutionSTFTLoss, STFTLoss
@@ -48,7 +49,7 @@ def LTPlugin(*args, **kwargs):
 
 __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
-    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "VThresholdSampler", "DiffusionModel",
+    "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "VThresholdSampler", "VStochasticSampler", "DiffusionModel",
     "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
 ]

@@ -2,7 +2,8 @@
 (DDIM-style loop) and `VInpainter` (RePaint-style resampling loop), API-compatible with
 /root/reference/audio_diffusion_pytorch/diffusion.py:15-30, :62-95, :133-190, :300-354.
 `VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own, and so is
-`VThresholdSampler`, which puts the reference's `clip` (dynamic thresholding, diffusion.py:36-54) inside the sampling loop.
+`VThresholdSampler`, which puts the reference's `clip` (dynamic thresholding, diffusion.py:36-54) inside the sampling loop,
+and `VStochasticSampler` (DDIM with eta > 0 on noise formed inside the update kernel).
 
 Differences from the reference are structural, not numerical:
   * noising (x_noisy, v_target) is one fused kernel (2 reads, 2 writes) instead of ~6 elementwise ops;
@@ -490,6 +491,142 @@ class VThresholdSampler(VMultistepSampler):
             return ops.clip_step(x, v, row, scale, out=out)
         hist_x0, hist_eps = hist
         return ops.clip_step(x, v, row, scale, hist_x0, hist_eps, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
+
+
+class VStochasticSampler(VSampler):
+    """DDIM with eta > 0 on the v-objective: the usual `sample(model, x, steps, eta)` loop of v-diffusion, optionally with
+    the predicted clean signal thresholded as in `VThresholdSampler` (the usual pair under classifier-free guidance).  Not
+    in the reference.
+
+        x0  = a_i x - b_i v            eps = b_i x + a_i v            x0c = x0, or clip(x0, dynamic_threshold)
+        cz_i = eta (b_{i+1} / b_i) sqrt(b_i^2 - b_{i+1}^2) / a_{i+1}      (0 where b_i = 0 or b_{i+1} = 0)
+        ce_i = sqrt(b_{i+1}^2 - cz_i^2)
+        x_{i+1} = a_{i+1} x0c + ce_i eps + cz_i z_i ,   z_i ~ N(0, 1)
+
+    eta = 0 is `VSampler` (ce = b_{i+1}, cz = 0); from pure noise with eta = 1 the first step is the DDPM step (ce = 0); the
+    last step (sigma = 0) adds no noise.  For eta in [0, 1] ce is real because b_i <= 1.  eps is kept from the raw v.
+
+    One step is one net evaluation and ONE update kernel (adp_v_step_eta, include/adp_sde.h) that forms z in registers
+    from the library's counter-based generator (include/adp_rng.h): no noise tensor is written or read, torch's generator
+    is not called, and the step replays from one hipGraph like `VSampler`'s.  `forward(..., seed=...)` fixes every draw of
+    the run on any backend: step i uses draw 1 + i of the seed, draw 0 is the start noise where the sampler draws it.  Each
+    step reads one row of a device table built once per run: (a_i, b_i, a_{i+1}, ce_i, cz_i), formed in float64 on the host
+    and rounded to float32 once, next to (seed_lo, seed_hi, draw, 0).  A captured step depends on whether eta > 0 and on the
+    threshold, not on the value of eta or the seed.  With eta == 0 the step is the parent's kernel (`VSampler`'s, or
+    `VThresholdSampler(order=1)`'s), bit for bit.
+
+    `dynamic_threshold`: None (no thresholding), 0.0 (static clamp to [-1, 1]) or q in (0, 1] (`VThresholdSampler`'s
+    quantile scale, five small launches in front of the update kernel).
+
+    Variation: `forward(x_noisy, num_steps, start=clip, strength=s)` starts from `a_s start + b_s noise` at the run's first
+    sigma and runs the sigmas `s * schedule(num_steps + 1)`; noise is x_noisy, or draw 0 of the seed where x_noisy is None.
+
+    Out of scope: a second-order stochastic update (there is no `order`), `VInpainter` and `ar.ARVSampler`."""
+
+    def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), eta: float = 1.0,
+                 dynamic_threshold: Optional[float] = None, use_graph: bool = True):
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0.0 <= eta <= 1.0:
+            raise ValueError(f"VStochasticSampler: eta must be a number in [0, 1]; got {eta!r}")
+        if dynamic_threshold is not None and (isinstance(dynamic_threshold, bool)
+                                              or not isinstance(dynamic_threshold, (int, float))
+                                              or not 0.0 <= dynamic_threshold <= 1.0):
+            raise ValueError("VStochasticSampler: dynamic_threshold must be None or a number in [0, 1]; "
+                             f"got {dynamic_threshold!r}")
+        super().__init__(net=net, schedule=schedule, use_graph=use_graph)
+        self.eta = float(eta)
+        self.dynamic_threshold = None if dynamic_threshold is None else float(dynamic_threshold)
+        self._run = (0, 1.0)  # (seed, strength) of the sampling run in progress: what `forward` hands to `_tables`
+
+    def _sigmas(self, num_steps: int, device) -> Tensor:
+        """The run's sigmas [N+1], float32 on the device: what the net is given."""
+        sigmas = self.schedule(num_steps + 1, device=device).to(torch.float32)
+        strength = self._run[1]
+        return sigmas if strength == 1.0 else sigmas * strength
+
+    def _tables(self, num_steps: int, b: int, device):
+        """sigma table [N+1, B] and the per-step table.  eta == 0: `VSampler`'s rows (a_i, b_i, a_{i+1}, b_{i+1}) [N, 4]
+        float32.  eta > 0: [N, 9] int32 words, the bits of (a_i, b_i, a_{i+1}, ce_i, cz_i) float32 next to
+        (seed_lo, seed_hi, 1 + i, 0).  The coefficients are formed in float64 on the host (one small device-to-host copy
+        per sampling run, none in the loop) and rounded to float32 once."""
+        sigmas = self._sigmas(num_steps, device)
+        sig = sigmas[:, None].expand(num_steps + 1, b).contiguous()
+        if self.eta == 0.0:
+            alphas, betas = self.get_alpha_beta(sigmas)
+            return sig, torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
+        s64 = sigmas.to(device="cpu", dtype=torch.float64)
+        phi = s64 * (pi / 2)
+        a, bt = torch.cos(phi), torch.sin(phi)
+        b0, b1, a1 = bt[:-1], bt[1:], a[1:]
+        if bool((b1 > b0).any()):
+            raise ValueError("VStochasticSampler: the schedule increases at step "
+                             f"{int((b1 > b0).nonzero()[0])} (b_{{i+1}} > b_i); the noise level must not grow")
+        zero = (b0 == 0) | (b1 == 0)
+        ratio = torch.where(zero, torch.zeros_like(b0), b1 / torch.where(zero, torch.ones_like(b0), b0))
+        num = self.eta * ratio * torch.sqrt((b0 * b0 - b1 * b1).clamp_min(0.0))
+        bad = (num > 0) & (s64[1:] == 1.0)
+        if bool(bad.any()):
+            raise ValueError(f"VStochasticSampler: step {int(bad.nonzero()[0])} adds noise towards sigma = 1, where "
+                             "a_{i+1} = 0 and cz is not defined")
+        cz = torch.where(num > 0, num / a1, torch.zeros_like(num))
+        ce = torch.sqrt((b1 * b1 - cz * cz).clamp_min(0.0))
+        coef = torch.stack([a[:-1], b0, a1, ce, cz], dim=1).to(torch.float32).contiguous()
+        rng = ops.rng_rows(self._run[0], range(1, 1 + num_steps))
+        table = torch.cat([coef.view(torch.int32), rng], dim=1).contiguous()
+        return sig, table.to(device)
+
+    def _step_key(self) -> Tuple:
+        return (self.eta > 0.0, self.dynamic_threshold)
+
+    def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
+        """(scale [B], select workspace) when the threshold is dynamic; left uninitialised, as `VThresholdSampler`'s are."""
+        if self.dynamic_threshold is None or self.dynamic_threshold == 0.0:
+            return ()
+        return (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x))
+
+    def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
+        noisy = row.dtype == torch.int32  # (the row of an eta > 0 table)
+        coef, rng = (row[:5].view(torch.float32), row[5:]) if noisy else (row, None)
+        scale = None
+        if bufs:
+            scale, ws = bufs
+            ops.clip_scale(x, self.dynamic_threshold, v=v, coef=coef, min_scale=1.0, ws=ws, out=scale)
+        if noisy:
+            return ops.v_step_eta(x, v, coef, rng, scale=scale, clip=self.dynamic_threshold is not None, out=out)
+        if self.dynamic_threshold is None:
+            return ops.v_step(x, v, row, out=out)
+        return ops.clip_step(x, v, row, scale, out=out)
+
+    @torch.no_grad()
+    def forward(self, x_noisy: Optional[Tensor], num_steps: int, show_progress: bool = False, *,
+                seed: Optional[int] = None, start: Optional[Tensor] = None, strength: float = 1.0, **kwargs) -> Tensor:
+        """`seed`: the integer all draws of this run follow; None = one drawn from torch's default CPU generator (so
+        torch.manual_seed governs it), without touching the device.  `start`, `strength`: variation (class docstring)."""
+        if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+            raise ValueError(f"VStochasticSampler: strength must be a number in (0, 1]; got {strength!r}")
+        if start is None:
+            if strength != 1.0:
+                raise ValueError("VStochasticSampler: strength != 1.0 needs start= (the clip to vary)")
+            if x_noisy is None:
+                raise ValueError("VStochasticSampler: x_noisy=None needs start= (pure noise is given by the caller)")
+        elif x_noisy is not None and x_noisy.shape != start.shape:
+            raise ValueError(f"VStochasticSampler: start must have x_noisy's shape {tuple(x_noisy.shape)}; "
+                             f"got {tuple(start.shape)}")
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())  # (a CPU tensor: no device sync)
+        self._run = (int(seed), float(strength))
+        try:
+            if start is not None:
+                with _on_device_of(start):
+                    src = start.to(torch.float32).contiguous()
+                    if x_noisy is not None:
+                        noise = x_noisy.to(torch.float32).contiguous()
+                    else:
+                        noise = ops.randn(src, ops.rng_rows(seed, [0])[0].to(src.device))
+                    first = self._sigmas(num_steps, src.device)[0].expand(src.shape[0]).contiguous()
+                    x_noisy = ops.v_noise(src, noise, first)[0]
+            return super().forward(x_noisy, num_steps, show_progress, **kwargs)
+        finally:
+            self._run = (0, 1.0)
 
 
 """ Inpainters """

@@ -867,6 +867,41 @@ def clip_step(x: Tensor, v: Tensor, coef: Tensor, scale: Optional[Tensor] = None
     return out if order == 1 else (out, hist_x0_out, hist_eps_out)
 
 
+# ---- include/adp_sde.h: the stochastic (DDIM-eta) v-sampler step on in-register Philox noise
+
+def v_step_eta(x: Tensor, v: Tensor, coef5: Tensor, rng4: Optional[Tensor], scale: Optional[Tensor] = None,
+               clip: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """One stochastic v-sampler update (adp_v_step_eta) on x [B, ...]: a1 x0c + ce eps + cz z with coef5 = device
+    (a0, b0, a1, ce, cz) and z the normals of the rng4 row's stream, formed in registers (the values `randn` gives for the
+    same row).  clip=False: x0c = x0.  clip=True: x0 is clamped to the item's scale and divided by it (scale=None: clamped
+    to [-1, 1]); eps comes from the raw v.  A row with cz = 0 does not read rng4, which may then be None (with cz != 0 a
+    missing row gives NaN).  `out` may be x."""
+    shape = tuple(int(s) for s in x.shape)
+    if len(shape) < 1:
+        raise ValueError("v_step_eta: x must be [B, ...]; got a scalar")
+    rows, per = shape[0], 1
+    for s in shape[1:]:
+        per *= s
+    for name, t in (("v", v), ("out", out)):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"v_step_eta: {name} must have x's shape {shape}; got {tuple(t.shape)}")
+    if coef5.dtype != torch.float32 or coef5.numel() != 5:
+        raise ValueError(f"v_step_eta: coef5 holds five float32 values (a0, b0, a1, ce, cz); got {coef5.dtype} "
+                         f"{tuple(coef5.shape)}")
+    if not isinstance(clip, bool):
+        raise ValueError(f"v_step_eta: clip must be a bool; got {clip!r}")
+    if scale is not None:
+        if not clip:
+            raise ValueError("v_step_eta: a scale needs clip=True")
+        if scale.numel() != rows:
+            raise ValueError(f"v_step_eta: scale must hold one value per item ({rows}); got {scale.numel()}")
+    row = None if rng4 is None else _rng_row_ptr("v_step_eta", rng4)
+    if out is None:
+        out = torch.empty_like(x)
+    _C.call("adp_v_step_eta", ptr(x), ptr(v), ptr(coef5), row, int(clip), ptr(scale), rows, per, ptr(out), _C.stream())
+    return out
+
+
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
     """y2 [2B, ...] -> y2[B:] + (y2[:B] - y2[B:]) * scale."""
     half = y2.numel() // 2

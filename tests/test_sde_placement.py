@@ -1,0 +1,160 @@
+"""The entry point of include/adp_sde.h with misaligned operands and guard bands (tests/placement.py), as
+tests/test_rng_placement.py does for include/adp_rng.h: every operand of a direct call through `_C.lib()` is placed by the test
+at the zero / all1 / mixed / single1 / single2 placements.  A placed call returns ADP_OK, gives the values of the restatement
+(tests/test_stochastic_sampler.py, within its STEP_TOL; the noise is `reference` of tests/test_rng.py, whose normals are
+within NORMAL_TOL of the kernel's) and leaves every guard, offset gap and input payload bit-identical.  Two items per call;
+two lengths: one on the 16-byte paths (which a misplaced pointer must leave) and an odd one, whose second item starts off the
+16-byte grid and inside a group of four."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from audio_diffusion_pytorch_amd import _C, ops
+from conftest import rel_err
+from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from test_rng import NORMAL_TOL, reference
+from test_stochastic_sampler import ROW, STEP_TOL, step_ref
+
+SEED, DRAW = 0x299F31D0A4093822, 9
+ROWS = 2
+LENGTHS = {"vec": 2048, "odd": 1001}
+# the restatement's z is the float64 generator: its distance to the kernel's normals, times cz, adds to the step's roundings
+# (NORMAL_TOL is absolute; the outputs' largest value is above 1, so it bounds the relative figure as well)
+TOL = STEP_TOL + NORMAL_TOL * float(ROW[4])
+
+
+def _data(n):
+    g = torch.Generator().manual_seed(n)
+    return [torch.randn(ROWS, n, generator=g) * 1.5 for _ in range(2)]
+
+
+def _step(mode):
+    def run(P, n):
+        x, v = _data(n)
+        scale = torch.tensor([1.0, 1.75]) if mode == "scale" else None
+        xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef5", ROW)
+        rd = P.arena.input("rng4", ops.rng_rows(SEED, [DRAW])[0], P._off("rng4", "in"))
+        sd = P.inp("scale", scale) if scale is not None else None
+        out = P.out("x_out", (ROWS, n))
+        code = _C.lib().adp_v_step_eta(p(xd), p(vd), p(cd), p(rd), int(mode != "plain"), p(sd), ROWS, n, p(out), _C.stream())
+        z = reference(SEED, DRAW, ROWS * n)[1][:ROWS * n].view(ROWS, n)
+        want = step_ref(x, v, ROW, z, clip=mode != "plain", scale=scale)
+        return code, lambda: [("x_out", rel_err(out, want), TOL)]
+    return run
+
+
+CASES = {mode: (_step(mode), "adp_v_step_eta") for mode in ("plain", "static", "scale")}
+
+
+def place_and_check(dev, name, length, plan, what):
+    fn, entry = CASES[name]
+    P = Placer(dev, plan)
+    code, figures = fn(P, LENGTHS[length])
+    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
+    problems = []
+    for label, err, bound in figures():
+        print(f"{entry} ({name}) {length} [{what}] {label}: {err:.3e} (bound {bound:.3e})")
+        if not err <= bound:
+            problems.append(f"{label}: {err:.3e} > {bound:.3e}")
+    P.arena.verify()   # raises PlacementError naming the operand and the span
+    assert not problems, f"{entry} ({name}) {length}, placement {what}:\n" + "\n".join(problems)
+    return P
+
+
+@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
+@pytest.mark.parametrize("length", list(LENGTHS))
+@pytest.mark.parametrize("name", list(CASES))
+def test_whole_call_placements(dev, name, length, kind):
+    place_and_check(dev, name, length, PLANS[kind], kind)
+
+
+@pytest.mark.parametrize("length", list(LENGTHS))
+@pytest.mark.parametrize("name", list(CASES))
+def test_single_operand_placements(dev, name, length):
+    """single1: each pointer operand alone at offset 1; single2: the output alone at offset 2 (the 8-byte phase)."""
+    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
+    for operand, role in base.operands:
+        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
+        if role in OUTPUT_ROLES:
+            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+
+
+def test_placement_does_not_change_the_values(dev):
+    """The arithmetic is per element and the stream belongs to the row, not to the addresses: the 16-byte and the
+    single-element paths agree bit for bit."""
+    outs = []
+    n = LENGTHS["odd"]
+    for kind in ("zero", "all1"):
+        P = Placer(dev, PLANS[kind])
+        code, _ = CASES["scale"][0](P, n)
+        assert code == 0
+        outs.append(P.arena.ops["x_out"].view.cpu().clone())
+    assert torch.equal(outs[0], outs[1])
+
+
+def test_refusals_in_order_write_nothing(dev):
+    ERR_SHAPE, ERR_ALIGN, ERR_NULL = -1, -3, -5
+    L, s = _C.lib(), _C.stream()
+    x = torch.zeros(2, 16, device=dev)
+    coef, scale, rng = torch.zeros(5, device=dev), torch.ones(2, device=dev), ops.rng_rows(1, [1])[0].to(dev)
+    out = torch.full((2, 16), 7.0, device=dev)
+    q = lambda t, off=0: t.data_ptr() + off
+    args = lambda: [q(x), q(x), q(coef), q(rng), 1, q(scale), 2, 16, q(out)]
+    for k in (0, 1, 2, 8):               # the pointers the call needs; rng4 (3) and scale (5) may be NULL
+        a = args()
+        a[k] = None
+        a[6] = -1                        # NULL is answered before the shape
+        assert L.adp_v_step_eta(*a, s) == ERR_NULL, k
+    for k, bad in ((6, -1), (7, -1), (4, 2), (4, -1), (6, 2 ** 62)):
+        a = args()
+        a[k] = bad
+        a[0] = q(x, 2)                   # the shape is answered before the alignment
+        assert L.adp_v_step_eta(*a, s) == ERR_SHAPE, (k, bad)
+    a = args()
+    a[4] = 0                             # a scale without clip
+    assert L.adp_v_step_eta(*a, s) == ERR_SHAPE
+    for k in (0, 1, 2, 3, 5, 8):
+        a = args()
+        a[k] = a[k] + 2
+        assert L.adp_v_step_eta(*a, s) == ERR_ALIGN, k
+    for k in (6, 7):                     # nothing to do: ADP_OK, nothing launched
+        a = args()
+        a[k] = 0
+        assert L.adp_v_step_eta(*a, s) == 0
+    assert torch.equal(out.cpu(), torch.full((2, 16), 7.0))
+    a = args()
+    a[3] = None                          # cz = 0: no row needed
+    assert L.adp_v_step_eta(*a, s) == 0 and torch.equal(out.cpu(), torch.zeros(2, 16))
+    assert _C.SDE_SIGNATURES["adp_v_step_eta"] == (ctypes.c_int, [_C.P] * 4 + [_C.I, _C.P, _C.I, _C.I, _C.P, _C.P])
+
+
+def test_every_sde_entry_point_is_placed():
+    assert {entry for _, entry in CASES.values()} == set(_C.SDE_SIGNATURES)
+    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES, _C.RNG_SIGNATURES,
+                  _C.CLIP_SIGNATURES, _C.GATED_SIGNATURES):
+        assert not set(_C.SDE_SIGNATURES) & set(other)
+
+
+def test_header_table_and_libraries_agree(emul):
+    """include/adp_sde.h <-> _C.SDE_SIGNATURES <-> what the built libraries export."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "adp_sde.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
+    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
+    assert declared == set(_C.SDE_SIGNATURES), declared ^ set(_C.SDE_SIGNATURES)
+    for name in declared:
+        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
+    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
+    hip_lib = ctypes.CDLL(_C.LIB_PATH)
+    for name in declared:
+        assert hasattr(hip_lib, name), name
+    csrc = os.path.join(root, "audio_diffusion_pytorch_amd", "csrc")
+    source = open(os.path.join(csrc, "sde.hip")).read()
+    assert '#include "adp_sde.h"' in source and '#include "philox.h"' in source
+    # one generator: rng.hip draws from the same header and states no Philox round of its own
+    rng = open(os.path.join(csrc, "rng.hip")).read()
+    assert '#include "philox.h"' in rng and "PHILOX_M0" not in rng and "PHILOX_M0" not in source
+    assert "adp_v_step_eta" not in open(os.path.join(root, "include", "adp_rng.h")).read()
