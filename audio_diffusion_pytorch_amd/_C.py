@@ -194,12 +194,18 @@ SDE_SIGNATURES = {
     "adp_v_step_eta": (c_int, [P, P, P, P, I, P, I, I, P, P]),
 }
 
+# the extension header include/adp_rf.h (rectified flow: the fused noising and the sampler update), one to one
+RF_SIGNATURES = {
+    "adp_rf_noise": (c_int, [P, P, P, I, I, P, P, P]),
+    "adp_rf_step": (c_int, [P, P, P, P, I, I, P, I, I, P, P, P]),
+}
+
 
 def _bind(path: str):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
-                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES, **SDE_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h / adp_sde.h declare
+                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES, **SDE_SIGNATURES, **RF_SIGNATURES}.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h / adp_sde.h / adp_rf.h declare
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -18,6 +18,7 @@ from .diffusion import (
 from .losses import MultiResolutionSTFTLoss, STFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
 from .optim import AdamW
+from .rf import LogitNormalDistribution, RFDiffusion, RFSampler
 from .unet import UNetV0Net
 
 XUNet = UNetV0Net
@@ -52,4 +53,5 @@ __all__ = [
     "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "VThresholdSampler", "VStochasticSampler", "DiffusionModel",
     "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
+    "RFDiffusion", "RFSampler", "LogitNormalDistribution",
 ]

@@ -74,6 +74,7 @@ class ARVDiffusion(Diffusion):
     # the captured-step cache and the conditions under which it may serve a call are VDiffusion's
     train_graphs = VDiffusion.train_graphs
     _graph_path_ok = VDiffusion._graph_path_ok
+    GRAPH_DISTRIBUTIONS = VDiffusion.GRAPH_DISTRIBUTIONS
 
     def forward(self, x: Tensor, noise: Optional[Tensor] = None, sigmas: Optional[Tensor] = None, **kwargs) -> Tensor:
         """Diffusion loss of the v-objective with one noise level per split.  `sigmas` ([b, 1, num_splits]) and `noise` (x's

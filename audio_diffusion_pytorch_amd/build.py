@@ -1,4 +1,4 @@
-"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of include/adp.h, include/adp_ar.h, include/adp_lt.h, include/adp_enc.h, include/adp_t5.h, include/adp_rng.h, include/adp_clip.h, include/adp_gated.h and include/adp_sde.h) in-tree with hipcc.
+"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of include/adp.h, include/adp_ar.h, include/adp_lt.h, include/adp_enc.h, include/adp_t5.h, include/adp_rng.h, include/adp_clip.h, include/adp_gated.h, include/adp_sde.h and include/adp_rf.h) in-tree with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the resulting
 .so travels to the GPU box with the repository snapshot.  No CUDA path, no hipify, no fallback.
@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libadp_hip.so")
-SOURCES = ["conv1d.hip", "conv_mm.hip", "conv_mm_m64.hip", "conv_mm_m32.hip", "conv_tile.hip", "conv_tilek.hip", "conv_tilek1.hip", "conv_mm4.hip", "wgrad_mm.hip", "conv_direct.hip", "wgrad_direct.hip", "norm.hip", "elementwise.hip", "resample.hip", "linear.hip", "attention.hip", "ctx_bank.hip", "lt.hip", "encoder.hip", "t5.hip", "gated.hip", "rng.hip", "clip.hip", "sde.hip", "probe.hip"]
+SOURCES = ["conv1d.hip", "conv_mm.hip", "conv_mm_m64.hip", "conv_mm_m32.hip", "conv_tile.hip", "conv_tilek.hip", "conv_tilek1.hip", "conv_mm4.hip", "wgrad_mm.hip", "conv_direct.hip", "wgrad_direct.hip", "norm.hip", "elementwise.hip", "resample.hip", "linear.hip", "attention.hip", "ctx_bank.hip", "lt.hip", "encoder.hip", "t5.hip", "gated.hip", "rng.hip", "clip.hip", "sde.hip", "rf.hip", "probe.hip"]
 
 
 def _newest_mtime(paths):

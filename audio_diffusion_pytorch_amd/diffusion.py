@@ -3,7 +3,8 @@
 /root/reference/audio_diffusion_pytorch/diffusion.py:15-30, :62-95, :133-190, :300-354.
 `VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own, and so is
 `VThresholdSampler`, which puts the reference's `clip` (dynamic thresholding, diffusion.py:36-54) inside the sampling loop,
-and `VStochasticSampler` (DDIM with eta > 0 on noise formed inside the update kernel).
+and `VStochasticSampler` (DDIM with eta > 0 on noise formed inside the update kernel).  Rectified flow (`RFDiffusion`,
+`RFSampler`) builds on these classes from rf.py.
 
 Differences from the reference are structural, not numerical:
   * noising (x_noisy, v_target) is one fused kernel (2 reads, 2 writes) instead of ~6 elementwise ops;
@@ -129,6 +130,8 @@ def fused_mse_loss(v_pred: Tensor, v_target: Tensor) -> Tensor:
 
 
 class VDiffusion(Diffusion):
+    GRAPH_DISTRIBUTIONS: Tuple[type, ...] = (UniformDistribution,)  # exact classes whose draw the replayed step may capture
+
     def __init__(self, net: nn.Module, sigma_distribution: Distribution = UniformDistribution(),
                  loss_fn: Any = F.mse_loss, use_graph: bool = True):
         """`use_graph` (not in the reference): replay the training step from hipGraphs where that is safe (graphed.py) --
@@ -166,7 +169,7 @@ class VDiffusion(Diffusion):
             return False
         if noise is not None and (not noise.is_cuda or noise.requires_grad or noise.shape != x.shape):
             return False
-        if type(self.sigma_distribution) is not UniformDistribution or os.environ.get("ADP_TRAIN_GRAPH", "1") == "0":
+        if type(self.sigma_distribution) not in self.GRAPH_DISTRIBUTIONS or os.environ.get("ADP_TRAIN_GRAPH", "1") == "0":
             return False
         if torch.cuda.is_current_stream_capturing():  # (a caller's own whole-step capture: bench.py, parallel.capture_step)
             return False

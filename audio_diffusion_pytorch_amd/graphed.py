@@ -13,10 +13,12 @@ sequence (one autograd node for the whole U-Net, no host reads), so `VDiffusion.
 the autograd node `_Replay` hands the flat buffer's per-parameter views to autograd, so AccumulateGrad, parameter hooks,
 gradient accumulation, `loss / k` scaling (the incoming gradient is a static input of graph B) and optimizers behave as in the
 eager step.  What is captured is exactly the eager path (`VDiffusion._forward_eager`), kernels and arithmetic unchanged.
-`ar.ARVDiffusion` replays its step through the same cache (it provides `loss_fn`, `sigma_distribution` and `_forward_eager`).
+`ar.ARVDiffusion` and `rf.RFDiffusion` replay their steps through the same cache (they provide `loss_fn`,
+`sigma_distribution` and `_forward_eager`); `RFDiffusion` also accepts `rf.LogitNormalDistribution`, keyed on its `graph_key()`.
 
 Taken only where it is safe, else the eager step runs as before (never an error): CUDA tensors, grad mode on, the stock
-`UniformDistribution`, inputs / conditioning tensors that do not require grad, keyword arguments that can be made static
+`UniformDistribution` (for `RFDiffusion` also `LogitNormalDistribution`), inputs / conditioning tensors that do not require
+grad, keyword arguments that can be made static
 (tensors, None, python scalars, lists of those), no data-parallel hook on the U-Net (its collectives are captured explicitly
 by parallel.capture_step), not already inside a stream capture, and no replayed loss of the same call structure still waiting
 for its backward (`(model(x1) + model(x2)).backward()`, or a stray forward between `loss = model(x)` and `loss.backward()`:
@@ -25,7 +27,8 @@ backpropagated or dropped).  `VDiffusion(use_graph=False)` or ADP_TRAIN_GRAPH=0 
 user loss_fn that syncs with the host) marks its call structure as eager-only.
 
 What a capture bakes in: the parameters' addresses (an entry is recaptured when one moves or is replaced), the `loss_fn`
-object and the `UniformDistribution`'s (vmin, vmax) (both part of the cache key), and the context-bank pointer tables of the
+object and the `UniformDistribution`'s (vmin, vmax) or the distribution's `graph_key()` (both part of the cache key), and
+the context-bank pointer tables of the
 nets under the module (attention.CtxBank; every entry keeps the tables it was captured with alive).  Any other Python-side
 state that a custom `net_t` reads in its forward is frozen at capture time as well.
 """
@@ -111,6 +114,13 @@ class _Replay(torch.autograd.Function):
         return (None,) + tuple(None if g is None else g.detach() for g in entry.grads)
 
 
+def _distribution_key(dist) -> tuple:
+    """What of the time / sigma distribution a captured step bakes in.  The stock `UniformDistribution`: its bounds.  Another
+    class whose draw is capturable says so by providing `graph_key()` (rf.LogitNormalDistribution: its name and parameters)."""
+    graph_key = getattr(dist, "graph_key", None)
+    return (dist.vmin, dist.vmax) if graph_key is None else tuple(graph_key())
+
+
 class TrainStepGraphs:
     """Cache of captured training steps of one diffusion module, keyed on the call STRUCTURE (shapes, kwarg names, tensor
     shapes / dtypes, python scalar values -- never the identity of an input) and on the module's loss_fn and sigma bounds,
@@ -133,7 +143,7 @@ class TrainStepGraphs:
         owner = self._owner()
         loss_fn, dist = owner.loss_fn, owner.sigma_distribution
         # (the captured step calls this loss_fn and draws sigmas from these bounds; the entry holds loss_fn, so its id is unique)
-        key = (tuple(x.shape), x.dtype, x.device, noise is not None, specs, id(loss_fn), dist.vmin, dist.vmax)
+        key = (tuple(x.shape), x.dtype, x.device, noise is not None, specs, id(loss_fn)) + _distribution_key(dist)
         if key in self.eager_only:
             return None
         all_params = tracked_parameters(owner)

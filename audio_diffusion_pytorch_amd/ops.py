@@ -902,6 +902,93 @@ def v_step_eta(x: Tensor, v: Tensor, coef5: Tensor, rng4: Optional[Tensor], scal
     return out
 
 
+# ---- include/adp_rf.h: rectified flow (the fused noising and the sampler update)
+
+def _rf_dims(what: str, x: Tensor) -> Tuple[int, int]:
+    shape = tuple(int(s) for s in x.shape)
+    if len(shape) < 1:
+        raise ValueError(f"{what}: x must be [B, ...]; got a scalar")
+    rows, per = shape[0], 1
+    for s in shape[1:]:
+        per *= s
+    return rows, per
+
+
+def rf_noise(x: Tensor, noise: Tensor, t: Tensor, x_t_out: Optional[Tensor] = None, u_out: Optional[Tensor] = None):
+    """(x_t, u) = ((1 - t_r) x + t_r noise, noise - x) for x [B, ...] and one time per item, t [B] (adp_rf_noise).  t = 0
+    returns x and t = 1 returns noise, bit for bit.  An output may be an input."""
+    rows, per = _rf_dims("rf_noise", x)
+    for name, other in (("noise", noise), ("x_t_out", x_t_out), ("u_out", u_out)):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"rf_noise: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    if t.dtype != torch.float32 or t.numel() != rows:
+        raise ValueError(f"rf_noise: t holds one float32 time per item ({rows}); got {t.dtype} {tuple(t.shape)}")
+    if x_t_out is None:
+        x_t_out = torch.empty_like(x)
+    if u_out is None:
+        u_out = torch.empty_like(x)
+    _C.call("adp_rf_noise", ptr(x), ptr(noise), ptr(t), rows, per, ptr(x_t_out), ptr(u_out), _C.stream())
+    return x_t_out, u_out
+
+
+def rf_table(times, order: int = 2) -> Tensor:
+    """The sampler's coefficient rows [N, 6] = (1, t_i, 1 - t_i, t_{i+1}, 1 - t_{i+1}, cb_i) for the times t_0 .. t_N
+    (include/adp_rf.h), float32 on the CPU: formed in float64 and rounded once.  cb_0 = 0, and every cb is 0 for order 1;
+    for order 2, cb_i = (t_{i+1} - t_i)**2 / (2 (t_i - t_{i-1})), the variable-step two-step Adams-Bashforth weight."""
+    if order not in (1, 2):
+        raise ValueError(f"rf_table: order must be 1 or 2; got {order!r}")
+    t = torch.as_tensor(times).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    if t.numel() < 1:
+        raise ValueError("rf_table: times must hold at least t_0")
+    n = t.numel() - 1
+    cb = torch.zeros(n, dtype=torch.float64)
+    if order == 2 and n > 1:
+        d = t[1:] - t[:-1]
+        g = d[:-1]
+        if bool((g == 0).any()):
+            raise ValueError(f"rf_table: the times repeat (zero step before step {int((g == 0).nonzero()[0]) + 1}); "
+                             "neighbouring times must differ")
+        cb[1:] = d[1:] * d[1:] / (2.0 * g)
+    one = torch.ones(n, dtype=torch.float64)
+    return torch.stack([one, t[:-1], 1.0 - t[:-1], t[1:], 1.0 - t[1:], cb], dim=1).to(torch.float32).contiguous()
+
+
+def rf_step(x: Tensor, u: Tensor, coef6: Tensor, scale: Optional[Tensor] = None, clip: bool = False, order: int = 1,
+            hist: Optional[Tensor] = None, out: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
+    """One rectified-flow sampler update (adp_rf_step) on x [B, ...] with coef6 = device (1, t0, 1 - t0, t1, 1 - t1, cb).
+    clip=False: x0c = x0.  clip=True: x0 is clamped to the item's scale and divided by it (scale=None: clamped to [-1, 1]);
+    eps comes from the raw u.  order=1 returns x_next and has no history; order=2 returns (x_next, w) and needs `hist` (the
+    previous step's w), which a row with cb = 0 does not read.  Every output may be its input."""
+    rows, per = _rf_dims("rf_step", x)
+    for name, other in (("u", u), ("hist", hist), ("out", out), ("hist_out", hist_out)):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"rf_step: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    if coef6.dtype != torch.float32 or coef6.numel() != 6:
+        raise ValueError(f"rf_step: coef6 holds six float32 values (1, t0, 1 - t0, t1, 1 - t1, cb); got {coef6.dtype} "
+                         f"{tuple(coef6.shape)}")
+    if order not in (1, 2) or isinstance(order, bool):
+        raise ValueError(f"rf_step: order must be 1 or 2; got {order!r}")
+    if not isinstance(clip, bool):
+        raise ValueError(f"rf_step: clip must be a bool; got {clip!r}")
+    if scale is not None:
+        if not clip:
+            raise ValueError("rf_step: a scale needs clip=True")
+        if scale.numel() != rows:
+            raise ValueError(f"rf_step: scale must hold one value per item ({rows}); got {scale.numel()}")
+    if order == 1:
+        if hist is not None or hist_out is not None:
+            raise ValueError("rf_step: the first-order step has no history")
+    elif hist is None:
+        raise ValueError("rf_step: the second-order step needs hist")
+    if out is None:
+        out = torch.empty_like(x)
+    if order == 2 and hist_out is None:
+        hist_out = torch.empty_like(x)
+    _C.call("adp_rf_step", ptr(x), ptr(u), ptr(hist), ptr(coef6), order, int(clip), ptr(scale), rows, per, ptr(out),
+            ptr(hist_out), _C.stream())
+    return out if order == 1 else (out, hist_out)
+
+
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
     """y2 [2B, ...] -> y2[B:] + (y2[:B] - y2[B:]) * scale."""
     half = y2.numel() // 2

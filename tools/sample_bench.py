@@ -6,7 +6,12 @@ select of adp_clip_scale, five launches, for q > 0 + adp_clip_step).  --sampler 
 through VStochasticSampler (1 step = 1 U-Net forward + adp_v_step_eta, its noise formed in the kernel; --threshold as for
 `threshold`, none if unset) with a fixed seed.  --repeats N times the run N times in one process and reports the median
 (every run is listed).  --also NAME ... measures further samplers on the same net in the same process, interleaved with the
-first per repeat, one result line each (an A/B on one box: numbers of different boxes differ by a few percent)."""
+first per repeat, one result line each (an A/B on one box: numbers of different boxes differ by a few percent).
+--sampler rf [--order n] [--threshold q] runs it through RFSampler (rectified flow: 1 step = 1 U-Net forward + adp_rf_step,
+behind the quantile select for q > 0); `vsampler` is another name of `v`.  --train N times the replayed training step instead:
+RFDiffusion against VDiffusion on the same net shape, N steps each per repeat, interleaved.  --kernels N times the update
+kernels alone (adp_rf_step order 1 / 2 against adp_v_step / adp_v_step2, adp_rf_noise against adp_v_noise) from the library's
+own per-launch event pairs, N launches each, median."""
 import argparse
 import json
 import os
@@ -19,7 +24,73 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 
-SAMPLERS = ["v", "multistep", "threshold", "stochastic"]
+SAMPLERS = ["v", "vsampler", "multistep", "threshold", "stochastic", "rf"]
+
+
+def train_bench(a, adp, dev):
+    """Replayed training steps (loss = model(x); loss.backward()) of RFDiffusion and VDiffusion, interleaved per repeat."""
+    models = {}
+    for name, diffusion_t in (("RFDiffusion", adp.RFDiffusion), ("VDiffusion", adp.VDiffusion)):
+        torch.manual_seed(0)
+        models[name] = adp.DiffusionModel(net_t=adp.UNetV0, in_channels=2, channels=bench.CHANNELS, factors=bench.FACTORS,
+                                          items=bench.ITEMS, diffusion_t=diffusion_t).to(dev)
+    x = torch.randn(a.batch, 2, bench.LENGTH, device=dev)
+
+    def steps(m, n):
+        for _ in range(n):
+            for p in m.parameters():
+                p.grad = None
+            m(x).backward()
+
+    for m in models.values():
+        steps(m, 3)  # warm-up + capture
+    times = {name: [] for name in models}
+    for _ in range(max(1, a.repeats)):
+        for name, m in models.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            steps(m, a.train)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / a.train)
+    for name, m in models.items():
+        ts = times[name]
+        graphs = m.diffusion.train_graphs()
+        print(json.dumps({"metric": f"training step ms ({name}, replayed)", "value": round(sorted(ts)[len(ts) // 2] * 1e3, 3),
+                          "batch": a.batch, "steps": a.train, "captures": graphs.captures, "replays": graphs.replays,
+                          "ms_per_step_runs": [round(t * 1e3, 3) for t in ts]}))
+
+
+def kernel_bench(a, adp, dev):
+    """The update kernels alone, from the event pair the library records around each launch while profiling."""
+    from audio_diffusion_pytorch_amd import _C, ops
+    g = torch.Generator().manual_seed(0)
+    x, u, h1, h2 = [torch.randn(a.batch, 2, bench.LENGTH, generator=g).to(dev) for _ in range(4)]
+    out, o1, o2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    t = torch.rand(a.batch, generator=g).to(dev)
+    row6 = ops.rf_table(torch.tensor([0.62, 0.55, 0.5]))[1].to(dev)
+    ab4, ab6 = torch.rand(4, generator=g).to(dev), torch.rand(6, generator=g).to(dev)
+    calls = {
+        "adp_rf_step order 1": lambda: ops.rf_step(x, u, row6, out=out),
+        "adp_v_step": lambda: ops.v_step(x, u, ab4, out=out),
+        "adp_rf_step order 2": lambda: ops.rf_step(x, u, row6, order=2, hist=h1, out=out, hist_out=o1),
+        "adp_v_step2": lambda: ops.v_step2(x, u, h1, h2, ab6, out=out, hist_x0_out=o1, hist_eps_out=o2),
+        "adp_rf_step order 1 static clamp": lambda: ops.rf_step(x, u, row6, clip=True, out=out),
+        "adp_rf_noise": lambda: ops.rf_noise(x, u, t, x_t_out=o1, u_out=o2),
+        "adp_v_noise": lambda: ops.v_noise(x, u, t),
+    }
+    for fn in calls.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in calls}
+    for _ in range(a.kernels):
+        for name, fn in calls.items():
+            _C.PROFILE = []
+            fn()
+            times[name] += [ms for _, _, _, ms in _C.profile_collect()]
+    for name, ts in times.items():
+        ts = sorted(ts)
+        print(json.dumps({"metric": f"kernel us ({name})", "value": round(ts[len(ts) // 2] * 1e3, 2),
+                          "min": round(ts[0] * 1e3, 2), "launches": len(ts), "shape": [a.batch, 2, bench.LENGTH]}))
 
 
 def main():
@@ -32,19 +103,24 @@ def main():
     ap.add_argument("--threshold", type=float, default=None,
                     help="--sampler threshold / stochastic: dynamic_threshold (0 = static clamp; threshold's default 0.995)")
     ap.add_argument("--eta", type=float, default=1.0, help="--sampler stochastic: eta in [0, 1]")
-    ap.add_argument("--order", type=int, default=None, help="--sampler multistep / threshold: order (their default if unset)")
+    ap.add_argument("--order", type=int, default=None,
+                    help="--sampler multistep / threshold / rf: order (their default if unset)")
+    ap.add_argument("--train", type=int, default=0, help="time N replayed training steps of RFDiffusion and VDiffusion instead")
+    ap.add_argument("--kernels", type=int, default=0, help="time N launches of each update kernel alone instead")
     ap.add_argument("--repeats", type=int, default=1)
     a = ap.parse_args()
     import audio_diffusion_pytorch_amd as adp
     dev = torch.device("cuda:0")
+    if a.train or a.kernels:
+        return (train_bench if a.train else kernel_bench)(a, adp, dev)
     torch.manual_seed(0)
     net = adp.UNetV0(dim=1, in_channels=2, channels=bench.CHANNELS, factors=bench.FACTORS, items=bench.ITEMS).to(dev)
     noise = torch.randn(a.batch, 2, bench.LENGTH).to(dev)
     names = [a.sampler] + list(a.also)
     samplers, kwargs, run_kw = [], [], []
     for name in names:
-        sampler_t = {"v": adp.VSampler, "multistep": adp.VMultistepSampler, "threshold": adp.VThresholdSampler,
-                     "stochastic": adp.VStochasticSampler}[name]
+        sampler_t = {"v": adp.VSampler, "vsampler": adp.VSampler, "multistep": adp.VMultistepSampler,
+                     "threshold": adp.VThresholdSampler, "stochastic": adp.VStochasticSampler, "rf": adp.RFSampler}[name]
         kw = {}
         if name == "threshold":
             kw["dynamic_threshold"] = 0.995 if a.threshold is None else a.threshold
@@ -52,7 +128,9 @@ def main():
             kw["eta"] = a.eta
             if a.threshold is not None:
                 kw["dynamic_threshold"] = a.threshold
-        if a.order is not None and name in ("multistep", "threshold"):
+        if name == "rf" and a.threshold is not None:
+            kw["dynamic_threshold"] = a.threshold
+        if a.order is not None and name in ("multistep", "threshold", "rf"):
             kw["order"] = a.order
         samplers.append(sampler_t(net=net, use_graph=bool(a.graph), **kw))
         kwargs.append(kw)
@@ -75,7 +153,7 @@ def main():
                "value": round(a.steps / dt, 2),
                "ms_per_step": round(dt / a.steps * 1e3, 3), "batch": a.batch, "num_steps": a.steps,
                "launch": "hipGraph replay" if a.graph else "eager", "finite": bool(torch.isfinite(out).all())}
-        if name != "v":
+        if name not in ("v", "vsampler"):
             res["sampler_kwargs"] = kw
         if a.repeats > 1:
             res["ms_per_step_runs"] = [round(t / a.steps * 1e3, 3) for t in ts]
