@@ -1,6 +1,7 @@
 // Dynamic thresholding (include/adp_clip.h): the exact per-item quantile of |x0| by a three-pass radix select, and the
 // v-sampler step that clips the predicted clean signal with it.
 //   adp_clip_scale : zero + 3 histogram passes (11 + 10 + 10 key bits) + finalize; x0 = a0 x - b0 v is formed on the fly
+//                    by clip_x0 of csrc/sampler_update.h, which every kernel that clamps x0 calls as well
 //   adp_clip_apply : out = clamp(x, -s, s) / s
 //   adp_clip_step  : first / second order update on the clipped x0, in place on x and the history
 // One workgroup histograms a span of CLIP_SPAN values of one row in LDS and merges its non-empty bins into the row's
@@ -9,8 +10,11 @@
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_clip.h"
+#include "sampler_update.h"
 
 namespace {
+
+using namespace upd;  // (csrc/sampler_update.h: clip_x0 and the clamps, shared with sde.hip and rf.hip)
 
 constexpr int CLIP_SPAN = 4096;                       // values of a row per workgroup and pass
 constexpr int CLIP_NB1 = 2048, CLIP_NB = 1024;        // bins of pass 1 (key bits 30..20) and of passes 2, 3 (10 bits each)
@@ -21,28 +25,15 @@ constexpr uint32_t KEY_INF = 0x7F800000u;
 
 #ifdef ADP_EMULATE
 inline void clip_count(uint32_t* p, uint32_t n) { *p += n; }  // (workgroups and lanes run one after another)
-inline float clip_fma(float a, float b, float c) { return fmaf(a, b, c); }
 #else
 __device__ __forceinline__ void clip_count(uint32_t* p, uint32_t n) { atomicAdd(p, n); }
-__device__ __forceinline__ float clip_fma(float a, float b, float c) { return __fmaf_rn(a, b, c); }
 #endif
 
-// THE predicted clean value: one product rounded, one fused multiply-add.  Every pass of the select and the step kernel
-// call this and nothing else, so that all of them see the same bits (a pass that rounded differently could send the select
-// into an empty bucket).
-__device__ __forceinline__ float clip_x0(float a0, float x, float b0, float v) { return clip_fma(a0, x, -(b0 * v)); }
-
+// the key a pass ranks: the bits of |x0|, x0 from the one function the step kernels clamp (sampler_update.h)
 template <bool HASV>
 __device__ __forceinline__ uint32_t clip_key(float a0, float b0, float x, float v) {
   return __float_as_uint(HASV ? clip_x0(a0, x, b0, v) : x) & 0x7FFFFFFFu;
 }
-
-// clamp(y, -s, s) / s; a NaN y or s stays NaN (torch.clamp's behaviour, which fminf / fmaxf do not have)
-__device__ __forceinline__ float clip_clamp_div(float y, float s) {
-  const float c = y < -s ? -s : (y > s ? s : y);
-  return c / s;
-}
-__device__ __forceinline__ float clip_clamp1(float y) { return y < -1.0f ? -1.0f : (y > 1.0f ? 1.0f : y); }
 
 // the prefix and the rank inside it of the two order statistics after a pass
 struct ClipSel {
@@ -210,11 +201,11 @@ __global__ __launch_bounds__(256) void clip_apply_kernel(const float* x, const f
       const f32x4 xv = *(const f32x4*)(xr + i);
       f32x4 y;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = clip_clamp_div(xv[k], s);
+      for (int k = 0; k < 4; ++k) y[k] = clamp_div(xv[k], s);
       *(f32x4*)(o + i) = y;
     }
   } else {
-    for (int64_t i = tid; i < per; i += nthreads) o[i] = clip_clamp_div(xr[i], s);
+    for (int64_t i = tid; i < per; i += nthreads) o[i] = clamp_div(xr[i], s);
   }
 }
 
@@ -226,12 +217,10 @@ struct ClipStepCoef {
 template <bool DYN, bool HIST>
 __device__ __forceinline__ float clip_step_elem(const ClipStepCoef& c, float s, float xv, float vv, float& hx, float& he) {
   const float x0 = clip_x0(c.a0, xv, c.b0, vv);
-  const float eps = clip_fma(c.b0, xv, c.a0 * vv);
-  const float x0c = DYN ? clip_clamp_div(x0, s) : clip_clamp1(x0);
-  // explicit multiply-adds: left to the compiler, the 16-byte and the single-element form contract differently and
-  // differ in the last bit
-  float xn = clip_fma(c.a1, x0c, c.b1 * eps);
-  if (HIST) xn = clip_fma(c.cb, eps - he, clip_fma(c.ca, x0c - hx, xn));
+  const float eps = fma_rn(c.b0, xv, c.a0 * vv);
+  const float x0c = clipped<DYN ? CLIP_SCALE : CLIP_STATIC>(x0, s);
+  float xn = fma_rn(c.a1, x0c, c.b1 * eps);
+  if (HIST) xn = fma_rn(c.cb, eps - he, fma_rn(c.ca, x0c - hx, xn));
   hx = x0c;
   he = eps;
   return xn;
@@ -307,8 +296,6 @@ __global__ __launch_bounds__(256) void clip_step_kernel(const float* x, const fl
     clip_step_body<DYN, ORDER2, false, VEC>(c, s, x, v, hx, he, per, xo, hxo, heo);
 }
 
-inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
-
 constexpr int64_t CLIP_MAX_PER = (int64_t)1 << 24, CLIP_MAX_ROWS = 65535;
 
 // blocks along a row for the elementwise kernels: one group of four per thread and pass, capped so that rows * blocks stays
@@ -331,15 +318,6 @@ void launch_pass(bool hasv, bool vec, dim3 grid, void* stream, const float* x, c
     ADP_LAUNCH((clip_pass_kernel<LEVEL, false, true>), grid, dim3(256), stream, x, v, coef, per, lo, hi, ws);
   else
     ADP_LAUNCH((clip_pass_kernel<LEVEL, false, false>), grid, dim3(256), stream, x, v, coef, per, lo, hi, ws);
-}
-
-template <bool DYN, bool ORDER2>
-void launch_step(bool vec, dim3 grid, void* stream, const float* x, const float* v, const float* hx, const float* he,
-                 const float* coef, const float* scale, int64_t per, float* xo, float* hxo, float* heo) {
-  if (vec)
-    ADP_LAUNCH((clip_step_kernel<DYN, ORDER2, true>), grid, dim3(256), stream, x, v, hx, he, coef, scale, per, xo, hxo, heo);
-  else
-    ADP_LAUNCH((clip_step_kernel<DYN, ORDER2, false>), grid, dim3(256), stream, x, v, hx, he, coef, scale, per, xo, hxo, heo);
 }
 
 }  // namespace
@@ -406,13 +384,13 @@ extern "C" int adp_clip_step(const float* x, const float* v, const float* hist_x
           !misaligned(hist_eps_out, 16);
   }
   const dim3 grid(row_grid(per), (unsigned)rows);
-  if (scale && order == 2)
-    launch_step<true, true>(vec, grid, stream, x, v, hist_x0, hist_eps, coef, scale, per, x_out, hist_x0_out, hist_eps_out);
-  else if (scale)
-    launch_step<true, false>(vec, grid, stream, x, v, hist_x0, hist_eps, coef, scale, per, x_out, hist_x0_out, hist_eps_out);
-  else if (order == 2)
-    launch_step<false, true>(vec, grid, stream, x, v, hist_x0, hist_eps, coef, scale, per, x_out, hist_x0_out, hist_eps_out);
-  else
-    launch_step<false, false>(vec, grid, stream, x, v, hist_x0, hist_eps, coef, scale, per, x_out, hist_x0_out, hist_eps_out);
+  with_flag(scale != nullptr, [&](auto DYN) {
+    with_flag(order == 2, [&](auto ORDER2) {
+      with_flag(vec, [&](auto VEC) {
+        ADP_LAUNCH((clip_step_kernel<DYN(), ORDER2(), VEC()>), grid, dim3(256), stream, x, v, hist_x0, hist_eps, coef, scale,
+                   per, x_out, hist_x0_out, hist_eps_out);
+      });
+    });
+  });
   return ADP_LAUNCH_OK();
 }

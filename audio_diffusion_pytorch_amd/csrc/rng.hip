@@ -5,16 +5,19 @@
 //   adp_randn              : the normals of a row's stream, 1 write
 //   adp_v_inpaint_step_rng : adp_v_inpaint_step with the noise formed in registers, 3 reads + 1 byte, 1 write
 // One thread owns one group of four elements per pass: one Philox call (ten rounds of two 32x32->64 multiplies) and two
-// Box-Muller pairs.  No LDS, no atomics, no cross-lane traffic; ordinary vector or single-element stores only.
+// Box-Muller pairs.  No LDS, no atomics, no cross-lane traffic; ordinary vector or single-element stores only.  The grid of
+// such a kernel and the alignment predicate are csrc/sampler_update.h's, shared with sde.hip and rf.hip.
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_rng.h"
 #include "inpaint_blend.h"
 #include "philox.h"
+#include "sampler_update.h"
 
 namespace {
 
 using namespace philox;  // (csrc/philox.h: the generator itself, shared with sde.hip)
+using namespace upd;     // (csrc/sampler_update.h: grid4 and misaligned)
 
 // VEC: out is 16-byte aligned -> whole groups leave as one 16-byte store; the tail group and the unaligned case as single
 // predicated stores
@@ -88,16 +91,6 @@ __global__ __launch_bounds__(256) void v_inpaint_rng_kernel(const float* x, cons
   }
 }
 
-// one group per thread and pass
-unsigned rng_grid(int64_t n) {
-  int64_t g = adp_cdiv(adp_cdiv(n, 4), 256);
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
-
 }  // namespace
 
 extern "C" int adp_philox_bits(const uint32_t* rng4, int64_t n_words, uint32_t* out, void* stream) {
@@ -106,9 +99,9 @@ extern "C" int adp_philox_bits(const uint32_t* rng4, int64_t n_words, uint32_t* 
   if (misaligned(rng4, 4) || misaligned(out, 4)) return ADP_ERR_ALIGN;
   if (n_words == 0) return ADP_OK;
   if (!misaligned(out, 16))
-    ADP_LAUNCH(philox_bits_kernel<true>, dim3(rng_grid(n_words)), dim3(256), stream, rng4, n_words, out);
+    ADP_LAUNCH(philox_bits_kernel<true>, dim3(grid4(n_words)), dim3(256), stream, rng4, n_words, out);
   else
-    ADP_LAUNCH(philox_bits_kernel<false>, dim3(rng_grid(n_words)), dim3(256), stream, rng4, n_words, out);
+    ADP_LAUNCH(philox_bits_kernel<false>, dim3(grid4(n_words)), dim3(256), stream, rng4, n_words, out);
   return ADP_LAUNCH_OK();
 }
 
@@ -118,9 +111,9 @@ extern "C" int adp_randn(const uint32_t* rng4, int64_t n, float* out, void* stre
   if (misaligned(rng4, 4) || misaligned(out, 4)) return ADP_ERR_ALIGN;
   if (n == 0) return ADP_OK;
   if (!misaligned(out, 16))
-    ADP_LAUNCH(randn_kernel<true>, dim3(rng_grid(n)), dim3(256), stream, rng4, n, out);
+    ADP_LAUNCH(randn_kernel<true>, dim3(grid4(n)), dim3(256), stream, rng4, n, out);
   else
-    ADP_LAUNCH(randn_kernel<false>, dim3(rng_grid(n)), dim3(256), stream, rng4, n, out);
+    ADP_LAUNCH(randn_kernel<false>, dim3(grid4(n)), dim3(256), stream, rng4, n, out);
   return ADP_LAUNCH_OK();
 }
 
@@ -135,8 +128,8 @@ extern "C" int adp_v_inpaint_step_rng(const float* x, const float* v, const floa
   const bool vec = !misaligned(x, 16) && !misaligned(v, 16) && !misaligned(source, 16) && !misaligned(x_out, 16) &&
                    !misaligned(mask, 4);
   if (vec)
-    ADP_LAUNCH(v_inpaint_rng_kernel<true>, dim3(rng_grid(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
+    ADP_LAUNCH(v_inpaint_rng_kernel<true>, dim3(grid4(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
   else
-    ADP_LAUNCH(v_inpaint_rng_kernel<false>, dim3(rng_grid(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
+    ADP_LAUNCH(v_inpaint_rng_kernel<false>, dim3(grid4(n)), dim3(256), stream, x, v, source, mask, ab4, rng4, n, x_out);
   return ADP_LAUNCH_OK();
 }

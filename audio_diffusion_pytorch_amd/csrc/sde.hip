@@ -3,44 +3,36 @@
 //   adp_v_step_eta : x_out = a1 clip(a0 x - b0 v) + ce (b0 x + a0 v) + cz z,  2 reads, 1 write
 // The shape is v_inpaint_rng_kernel's: one thread owns one group of four elements per pass -- one Philox call and two
 // Box-Muller pairs -- in a grid-stride loop over the groups.  A row with cz == 0 skips the draw.  No LDS, no atomics, no
-// cross-lane traffic; ordinary vector or single-element stores only.
+// cross-lane traffic; ordinary vector or single-element stores only.  The arithmetic of x0 and its clamps, the per-item
+// scale of a group and the grid are csrc/sampler_update.h's, shared with clip.hip and rf.hip.
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_sde.h"
 #include "philox.h"
+#include "sampler_update.h"
 
 namespace {
 
 using namespace philox;
-
-#ifdef ADP_EMULATE
-inline float sde_fma(float a, float b, float c) { return fmaf(a, b, c); }
-#else
-__device__ __forceinline__ float sde_fma(float a, float b, float c) { return __fmaf_rn(a, b, c); }
-#endif
+using namespace upd;
 
 struct SdeCoef {
   float a0, b0, a1, ce, cz;
 };
 
-enum { CLIP_NONE = 0, CLIP_STATIC = 1, CLIP_SCALE = 2 };
-
-// One element.  The multiply-adds are explicit: left to the compiler, the 16-byte and the single-element form could contract
-// differently.  x0 is clip.hip's clip_x0 (fma(a0, x, -(b0 * v))): the scale was selected from those bits.  The clamps are
-// clip.hip's as well: a NaN x0 or scale stays NaN.
+// One element.  x0 and its clamps are sampler_update.h's clip_x0 and clipped, the ones clip.hip's select ranks and
+// adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale stays NaN.
 template <int CLIP>
 __device__ __forceinline__ float sde_elem(const SdeCoef& c, float s, float xv, float vv, float z, bool noisy) {
-  const float x0 = sde_fma(c.a0, xv, -(c.b0 * vv));
-  const float eps = sde_fma(c.b0, xv, c.a0 * vv);
-  float x0c = x0;
-  if (CLIP == CLIP_STATIC) x0c = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);
-  if (CLIP == CLIP_SCALE) x0c = (x0 < -s ? -s : (x0 > s ? s : x0)) / s;
-  const float xn = sde_fma(c.a1, x0c, c.ce * eps);
-  return noisy ? sde_fma(c.cz, z, xn) : xn;
+  const float x0 = clip_x0(c.a0, xv, c.b0, vv);
+  const float eps = fma_rn(c.b0, xv, c.a0 * vv);
+  const float x0c = clipped<CLIP>(x0, s);
+  const float xn = fma_rn(c.a1, x0c, c.ce * eps);
+  return noisy ? fma_rn(c.cz, z, xn) : xn;
 }
 
-// VEC: x, v and xo are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per]; a group may straddle items (one 64-bit
-// division per group, then a walk over the item boundaries inside it).
+// VEC: x, v and xo are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per]; a group may straddle items
+// (item_values4).
 template <int CLIP, bool VEC>
 __global__ __launch_bounds__(256) void v_step_eta_kernel(const float* x, const float* v, const float* coef5,
                                                          const uint32_t* rng4, const float* scale, int64_t n, int64_t per,
@@ -63,21 +55,7 @@ __global__ __launch_bounds__(256) void v_step_eta_kernel(const float* x, const f
       }
     }
     float s[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-    if (CLIP == CLIP_SCALE) {
-      int64_t item = e / per, next = (item + 1) * per;  // (e < n: item < rows)
-      float si = scale[item];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (e + k < n) {
-          while (e + k >= next) {  // (e + k < n: the walk stays below rows)
-            ++item;
-            next += per;
-            si = scale[item];
-          }
-          s[k] = si;
-        }
-      }
-    }
+    if (CLIP == CLIP_SCALE) item_values4(scale, e, n, per, s);
     if (VEC && e + 4 <= n) {
       const f32x4 xv = *(const f32x4*)(x + e), vv = *(const f32x4*)(v + e);
       f32x4 o;
@@ -92,43 +70,24 @@ __global__ __launch_bounds__(256) void v_step_eta_kernel(const float* x, const f
   }
 }
 
-// one group per thread and pass
-unsigned sde_grid(int64_t n) {
-  int64_t g = adp_cdiv(adp_cdiv(n, 4), 256);
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-inline bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
-
-template <int CLIP>
-void launch_step(bool vec, void* stream, const float* x, const float* v, const float* coef5, const uint32_t* rng4,
-                 const float* scale, int64_t n, int64_t per, float* xo) {
-  if (vec)
-    ADP_LAUNCH((v_step_eta_kernel<CLIP, true>), dim3(sde_grid(n)), dim3(256), stream, x, v, coef5, rng4, scale, n, per, xo);
-  else
-    ADP_LAUNCH((v_step_eta_kernel<CLIP, false>), dim3(sde_grid(n)), dim3(256), stream, x, v, coef5, rng4, scale, n, per, xo);
-}
-
 }  // namespace
 
 extern "C" int adp_v_step_eta(const float* x, const float* v, const float* coef5, const uint32_t* rng4, int64_t clip,
                               const float* scale, int64_t rows, int64_t per, float* x_out, void* stream) {
   if (!x || !v || !coef5 || !x_out) return ADP_ERR_NULL;
   if (rows < 0 || per < 0 || (clip != 0 && clip != 1) || (clip == 0 && scale)) return ADP_ERR_SHAPE;
-  if (per > 0 && rows > INT64_MAX / per) return ADP_ERR_SHAPE;
+  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
   if (misaligned(x, 4) || misaligned(v, 4) || misaligned(coef5, 4) || misaligned(x_out, 4) ||
       (rng4 && misaligned(rng4, 4)) || (scale && misaligned(scale, 4)))
     return ADP_ERR_ALIGN;
   const int64_t n = rows * per;
   if (n == 0) return ADP_OK;
   const bool vec = !misaligned(x, 16) && !misaligned(v, 16) && !misaligned(x_out, 16);
-  if (clip == 0)
-    launch_step<CLIP_NONE>(vec, stream, x, v, coef5, rng4, scale, n, per, x_out);
-  else if (!scale)
-    launch_step<CLIP_STATIC>(vec, stream, x, v, coef5, rng4, scale, n, per, x_out);
-  else
-    launch_step<CLIP_SCALE>(vec, stream, x, v, coef5, rng4, scale, n, per, x_out);
+  with_clip(clip, scale, [&](auto CLIP) {
+    with_flag(vec, [&](auto VEC) {
+      ADP_LAUNCH((v_step_eta_kernel<CLIP(), VEC()>), dim3(grid4(n)), dim3(256), stream, x, v, coef5, rng4, scale, n, per,
+                 x_out);
+    });
+  });
   return ADP_LAUNCH_OK();
 }

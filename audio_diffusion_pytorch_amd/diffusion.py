@@ -66,6 +66,17 @@ def alpha_beta(sigmas: Tensor) -> Tuple[Tensor, Tensor]:
     return torch.cos(angle), torch.sin(angle)
 
 
+def _is_number(v) -> bool:
+    """A number, not a bool: what the samplers' scalar arguments must be."""
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _ab_rows(alphas: Tensor, betas: Tensor, ahead: int = 1) -> Tensor:
+    """The first-order rows (a_i, b_i, a_j, b_j) [N, 4] for j = i + ahead, from the N + 1 values of the schedule."""
+    n = alphas.shape[0] - 1
+    return torch.stack([alphas[:-1], betas[:-1], alphas[ahead:n + ahead], betas[ahead:n + ahead]], dim=1).contiguous()
+
+
 def pad_dims(x: Tensor, ndim: int) -> Tensor:
     """Pads `ndim` dimensions of size 1 to the right of the tensor (diffusion.py:36-38)."""
     return x.view(*x.shape, *((1,) * ndim))
@@ -284,8 +295,7 @@ class VSampler(_CapturedSteps, Sampler):
         The schedule is a pure function of num_steps, so nothing here (or in the loop) syncs with the host."""
         sigmas = self.schedule(num_steps + 1, device=device).to(torch.float32)
         alphas, betas = self.get_alpha_beta(sigmas)
-        ab = torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
-        return sigmas[:, None].expand(num_steps + 1, b).contiguous(), ab
+        return sigmas[:, None].expand(num_steps + 1, b).contiguous(), _ab_rows(alphas, betas)
 
     def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
         """Tensors of x's shape that the step update carries from one step to the next (a subclass's history); owned by the
@@ -404,7 +414,7 @@ class VMultistepSampler(VSampler):
     `order=1` is `VSampler`'s arithmetic (A/B in one class)."""
 
     def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), order: int = 2, use_graph: bool = True):
-        if order not in (1, 2):
+        if not _is_number(order) or order not in (1, 2):
             raise ValueError(f"VMultistepSampler: order must be 1 or 2; got {order!r}")
         super().__init__(net=net, schedule=schedule, use_graph=use_graph)
         self.order = order
@@ -441,7 +451,41 @@ class VMultistepSampler(VSampler):
         return ops.v_step2(x, v, hist_x0, hist_eps, row, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
 
 
-class VThresholdSampler(VMultistepSampler):
+class _Thresholded:
+    """The dynamic-threshold glue of `VThresholdSampler`, `VStochasticSampler` and `rf.RFSampler` (mixed into a `VSampler`
+    that sets `self.dynamic_threshold`): None = no clipping, 0.0 = the static clamp to [-1, 1], q in (0, 1] = the per-item
+    quantile scale of include/adp_clip.h, selected in front of the update kernel from the step's own (x, v, coefficient row)."""
+
+    @staticmethod
+    def _threshold(owner: str, dynamic_threshold, none_ok: bool) -> Optional[float]:
+        """The checked constructor argument as a float (or None where the class allows it)."""
+        if dynamic_threshold is None and none_ok:
+            return None
+        if not (_is_number(dynamic_threshold) and 0.0 <= dynamic_threshold <= 1.0):
+            raise ValueError(f"{owner}: dynamic_threshold must be {'None or ' if none_ok else ''}a number in [0, 1]; "
+                             f"got {dynamic_threshold!r}")
+        return float(dynamic_threshold)
+
+    def _dynamic(self) -> bool:
+        return self.dynamic_threshold is not None and self.dynamic_threshold > 0.0
+
+    def _threshold_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
+        """(scale [B], select workspace) when the threshold is dynamic: they lead the class's own step buffers.  Left
+        uninitialised: every step zeroes the workspace it uses and writes the scale before reading it."""
+        if not self._dynamic():
+            return ()
+        return (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x))
+
+    def _threshold_scale(self, x: Tensor, v: Tensor, coef: Tensor, bufs: Tuple[Tensor, ...]):
+        """(this step's scale [B] or None, the step buffers behind `_threshold_buffers`'); coef: the row holding (a0, b0)."""
+        if not self._dynamic():
+            return None, bufs
+        scale, ws = bufs[:2]
+        ops.clip_scale(x, self.dynamic_threshold, v=v, coef=coef, min_scale=1.0, ws=ws, out=scale)
+        return scale, bufs[2:]
+
+
+class VThresholdSampler(_Thresholded, VMultistepSampler):
     """`VSampler` (order=1) or `VMultistepSampler` (order=2) with the predicted clean signal thresholded at every step: what
     keeps a bounded signal (audio in [-1, 1]) bounded under classifier-free guidance, where x0 = a x - b v leaves the range at
     the noisy end of the schedule.  Not in the reference, whose `clip` (diffusion.py:41-54) has no caller.
@@ -462,41 +506,28 @@ class VThresholdSampler(VMultistepSampler):
 
     def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), dynamic_threshold: float = 0.995,
                  order: int = 1, use_graph: bool = True):
-        if order not in (1, 2):
+        if not _is_number(order) or order not in (1, 2):
             raise ValueError(f"VThresholdSampler: order must be 1 or 2; got {order!r}")
-        if isinstance(dynamic_threshold, bool) or not isinstance(dynamic_threshold, (int, float)) \
-                or not 0.0 <= dynamic_threshold <= 1.0:
-            raise ValueError(f"VThresholdSampler: dynamic_threshold must be a number in [0, 1]; got {dynamic_threshold!r}")
+        threshold = self._threshold("VThresholdSampler", dynamic_threshold, none_ok=False)
         super().__init__(net=net, schedule=schedule, order=order, use_graph=use_graph)
-        self.dynamic_threshold = float(dynamic_threshold)
-
-    def _tables(self, num_steps: int, b: int, device):
-        """`VMultistepSampler`'s tables: rows of 4 coefficients for order 1, of 6 for order 2."""
-        return super()._tables(num_steps, b, device)
+        self.dynamic_threshold = threshold
 
     def _step_key(self) -> Tuple:
         return (float(self.dynamic_threshold), self.order)
 
     def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
-        """(scale [B], select workspace) when the threshold is dynamic, then `VMultistepSampler`'s history.  All left
-        uninitialised: every step zeroes the workspace it uses and writes the scale before reading it."""
-        hist = super()._step_buffers(x)
-        if self.dynamic_threshold == 0.0:
-            return hist
-        return (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x)) + tuple(hist)
+        """The threshold's buffers, then `VMultistepSampler`'s history."""
+        return self._threshold_buffers(x) + tuple(super()._step_buffers(x))
 
     def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
-        scale, hist = None, bufs
-        if len(bufs) > (0 if self.order == 1 else 2):  # the dynamic threshold's buffers lead the history
-            scale, ws, hist = bufs[0], bufs[1], bufs[2:]
-            ops.clip_scale(x, self.dynamic_threshold, v=v, coef=row, min_scale=1.0, ws=ws, out=scale)
+        scale, hist = self._threshold_scale(x, v, row, bufs)
         if self.order == 1:
             return ops.clip_step(x, v, row, scale, out=out)
         hist_x0, hist_eps = hist
         return ops.clip_step(x, v, row, scale, hist_x0, hist_eps, out=out, hist_x0_out=hist_x0, hist_eps_out=hist_eps)[0]
 
 
-class VStochasticSampler(VSampler):
+class VStochasticSampler(_Thresholded, VSampler):
     """DDIM with eta > 0 on the v-objective: the usual `sample(model, x, steps, eta)` loop of v-diffusion, optionally with
     the predicted clean signal thresholded as in `VThresholdSampler` (the usual pair under classifier-free guidance).  Not
     in the reference.
@@ -528,16 +559,12 @@ class VStochasticSampler(VSampler):
 
     def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), eta: float = 1.0,
                  dynamic_threshold: Optional[float] = None, use_graph: bool = True):
-        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0.0 <= eta <= 1.0:
+        if not _is_number(eta) or not 0.0 <= eta <= 1.0:
             raise ValueError(f"VStochasticSampler: eta must be a number in [0, 1]; got {eta!r}")
-        if dynamic_threshold is not None and (isinstance(dynamic_threshold, bool)
-                                              or not isinstance(dynamic_threshold, (int, float))
-                                              or not 0.0 <= dynamic_threshold <= 1.0):
-            raise ValueError("VStochasticSampler: dynamic_threshold must be None or a number in [0, 1]; "
-                             f"got {dynamic_threshold!r}")
+        threshold = self._threshold("VStochasticSampler", dynamic_threshold, none_ok=True)
         super().__init__(net=net, schedule=schedule, use_graph=use_graph)
         self.eta = float(eta)
-        self.dynamic_threshold = None if dynamic_threshold is None else float(dynamic_threshold)
+        self.dynamic_threshold = threshold
         self._run = (0, 1.0)  # (seed, strength) of the sampling run in progress: what `forward` hands to `_tables`
 
     def _sigmas(self, num_steps: int, device) -> Tensor:
@@ -554,8 +581,7 @@ class VStochasticSampler(VSampler):
         sigmas = self._sigmas(num_steps, device)
         sig = sigmas[:, None].expand(num_steps + 1, b).contiguous()
         if self.eta == 0.0:
-            alphas, betas = self.get_alpha_beta(sigmas)
-            return sig, torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
+            return sig, _ab_rows(*self.get_alpha_beta(sigmas))
         s64 = sigmas.to(device="cpu", dtype=torch.float64)
         phi = s64 * (pi / 2)
         a, bt = torch.cos(phi), torch.sin(phi)
@@ -581,18 +607,12 @@ class VStochasticSampler(VSampler):
         return (self.eta > 0.0, self.dynamic_threshold)
 
     def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
-        """(scale [B], select workspace) when the threshold is dynamic; left uninitialised, as `VThresholdSampler`'s are."""
-        if self.dynamic_threshold is None or self.dynamic_threshold == 0.0:
-            return ()
-        return (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x))
+        return self._threshold_buffers(x)
 
     def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
         noisy = row.dtype == torch.int32  # (the row of an eta > 0 table)
         coef, rng = (row[:5].view(torch.float32), row[5:]) if noisy else (row, None)
-        scale = None
-        if bufs:
-            scale, ws = bufs
-            ops.clip_scale(x, self.dynamic_threshold, v=v, coef=coef, min_scale=1.0, ws=ws, out=scale)
+        scale, _ = self._threshold_scale(x, v, coef, bufs)
         if noisy:
             return ops.v_step_eta(x, v, coef, rng, scale=scale, clip=self.dynamic_threshold is not None, out=out)
         if self.dynamic_threshold is None:
@@ -604,7 +624,7 @@ class VStochasticSampler(VSampler):
                 seed: Optional[int] = None, start: Optional[Tensor] = None, strength: float = 1.0, **kwargs) -> Tensor:
         """`seed`: the integer all draws of this run follow; None = one drawn from torch's default CPU generator (so
         torch.manual_seed governs it), without touching the device.  `start`, `strength`: variation (class docstring)."""
-        if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+        if not _is_number(strength) or not 0.0 < strength <= 1.0:
             raise ValueError(f"VStochasticSampler: strength must be a number in (0, 1]; got {strength!r}")
         if start is None:
             if strength != 1.0:
@@ -695,9 +715,7 @@ class VInpainter(_CapturedSteps, Inpainter):
         sigmas = self.schedule(num_steps + 1, device=device).to(torch.float32)
         alphas, betas = self.get_alpha_beta(sigmas)
         sig = sigmas[:, None].expand(num_steps + 1, b).contiguous()
-        ab_stay = torch.stack([alphas[:-1], betas[:-1], alphas[:-1], betas[:-1]], dim=1).contiguous()
-        ab_next = torch.stack([alphas[:-1], betas[:-1], alphas[1:], betas[1:]], dim=1).contiguous()
-        return sig, ab_stay, ab_next
+        return sig, _ab_rows(alphas, betas, ahead=0), _ab_rows(alphas, betas)
 
     def _run(self, source, mask, num_steps, num_resamples, show_progress, x_noisy, kwargs) -> Tensor:
         x = (x_noisy if x_noisy is not None else torch.randn_like(source)).contiguous()

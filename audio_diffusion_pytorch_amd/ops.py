@@ -762,17 +762,29 @@ def v_inpaint_step_rng(x: Tensor, v: Tensor, source: Tensor, mask_u8: Tensor, ab
 CLIP_MAX_PER = 1 << 24  # per - 1 is exact in float32 up to here (torch.quantile's own limit)
 
 
-def _clip_dims(what: str, x) -> Tuple[int, int]:
-    """(rows, per) of a [B, ...] batch, from its shape alone (nothing is read or launched before the checks pass)."""
+def _item_dims(what: str, x, max_per: Optional[int] = None) -> Tuple[int, int]:
+    """(rows, per) of a [B, ...] batch, from its shape alone (nothing is read or launched before the checks pass).
+    max_per: the quantile's cap on the values of one item."""
     shape = tuple(int(s) for s in x.shape)
     if len(shape) < 1:
         raise ValueError(f"{what}: x must be [B, ...]; got a scalar")
     rows, per = shape[0], 1
     for s in shape[1:]:
         per *= s
-    if per > CLIP_MAX_PER:
-        raise ValueError(f"{what}: {per} values per item; the quantile is defined for at most 2**24 = {CLIP_MAX_PER}")
+    if max_per is not None and per > max_per:
+        raise ValueError(f"{what}: {per} values per item; the quantile is defined for at most 2**24 = {max_per}")
     return rows, per
+
+
+def _check_clip(what: str, clip, scale, rows: int) -> None:
+    """The clip / scale arguments of a sampler update: clip is a bool, and a scale needs it and holds one value per item."""
+    if not isinstance(clip, bool):
+        raise ValueError(f"{what}: clip must be a bool; got {clip!r}")
+    if scale is not None:
+        if not clip:
+            raise ValueError(f"{what}: a scale needs clip=True")
+        if scale.numel() != rows:
+            raise ValueError(f"{what}: scale must hold one value per item ({rows}); got {scale.numel()}")
 
 
 def clip_rank(q: float, per: int) -> Tuple[int, float]:
@@ -788,7 +800,7 @@ def clip_rank(q: float, per: int) -> Tuple[int, float]:
 
 def clip_ws(x: Tensor) -> Tensor:
     """The workspace `clip_scale` needs for x [B, ...] (uninitialised: the call zeroes what it uses)."""
-    rows, per = _clip_dims("clip_ws", x)
+    rows, per = _item_dims("clip_ws", x, CLIP_MAX_PER)
     return _ws(_C.query("adp_clip_ws_bytes", rows, per), x)
 
 
@@ -797,7 +809,7 @@ def clip_scale(x: Tensor, q: float, v: Optional[Tensor] = None, coef: Optional[T
     """scale [B] = max(quantile_q(|y|), min_scale) per item of x [B, ...] (adp_clip_scale), y = x, or coef[0] x - coef[1] v
     when v is given (coef: device row whose first two values are a0, b0).  torch.quantile's linear rule, exact selection,
     no sort, no host read; a row holding a NaN gets NaN."""
-    rows, per = _clip_dims("clip_scale", x)
+    rows, per = _item_dims("clip_scale", x, CLIP_MAX_PER)
     if (v is None) != (coef is None):
         raise ValueError("clip_scale: v and coef go together")
     if v is not None and v.shape != x.shape:
@@ -823,7 +835,7 @@ def clip_scale(x: Tensor, q: float, v: Optional[Tensor] = None, coef: Optional[T
 
 def clip_apply(x: Tensor, scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """clamp(x, -s, s) / s with one s per item of x [B, ...] (adp_clip_apply).  `out` may be x."""
-    rows, per = _clip_dims("clip_apply", x)
+    rows, per = _item_dims("clip_apply", x, CLIP_MAX_PER)
     if scale.numel() != rows:
         raise ValueError(f"clip_apply: scale must hold one value per item ({rows}); got {scale.numel()}")
     if out is None:
@@ -841,7 +853,7 @@ def clip_step(x: Tensor, v: Tensor, coef: Tensor, scale: Optional[Tensor] = None
     divided by it (scale=None: clamped to [-1, 1]); eps comes from the raw v.  A coef row of 4 values is the first-order
     step and returns x_next; one of 6 values (a0, b0, a1, b1, ca, cb) the second-order step on the history and returns
     (x_next, clipped x0, eps).  Every output may be its input; a row with ca = cb = 0 does not read the history."""
-    rows, per = _clip_dims("clip_step", x)
+    rows, per = _item_dims("clip_step", x, CLIP_MAX_PER)
     if coef.numel() not in (4, 6):
         raise ValueError(f"clip_step: coef holds (a0, b0, a1, b1) or (a0, b0, a1, b1, ca, cb); got {coef.numel()} values")
     order = 1 if coef.numel() == 4 else 2
@@ -876,25 +888,14 @@ def v_step_eta(x: Tensor, v: Tensor, coef5: Tensor, rng4: Optional[Tensor], scal
     same row).  clip=False: x0c = x0.  clip=True: x0 is clamped to the item's scale and divided by it (scale=None: clamped
     to [-1, 1]); eps comes from the raw v.  A row with cz = 0 does not read rng4, which may then be None (with cz != 0 a
     missing row gives NaN).  `out` may be x."""
-    shape = tuple(int(s) for s in x.shape)
-    if len(shape) < 1:
-        raise ValueError("v_step_eta: x must be [B, ...]; got a scalar")
-    rows, per = shape[0], 1
-    for s in shape[1:]:
-        per *= s
+    rows, per = _item_dims("v_step_eta", x)
     for name, t in (("v", v), ("out", out)):
         if t is not None and t.shape != x.shape:
-            raise ValueError(f"v_step_eta: {name} must have x's shape {shape}; got {tuple(t.shape)}")
+            raise ValueError(f"v_step_eta: {name} must have x's shape {tuple(x.shape)}; got {tuple(t.shape)}")
     if coef5.dtype != torch.float32 or coef5.numel() != 5:
         raise ValueError(f"v_step_eta: coef5 holds five float32 values (a0, b0, a1, ce, cz); got {coef5.dtype} "
                          f"{tuple(coef5.shape)}")
-    if not isinstance(clip, bool):
-        raise ValueError(f"v_step_eta: clip must be a bool; got {clip!r}")
-    if scale is not None:
-        if not clip:
-            raise ValueError("v_step_eta: a scale needs clip=True")
-        if scale.numel() != rows:
-            raise ValueError(f"v_step_eta: scale must hold one value per item ({rows}); got {scale.numel()}")
+    _check_clip("v_step_eta", clip, scale, rows)
     row = None if rng4 is None else _rng_row_ptr("v_step_eta", rng4)
     if out is None:
         out = torch.empty_like(x)
@@ -904,20 +905,10 @@ def v_step_eta(x: Tensor, v: Tensor, coef5: Tensor, rng4: Optional[Tensor], scal
 
 # ---- include/adp_rf.h: rectified flow (the fused noising and the sampler update)
 
-def _rf_dims(what: str, x: Tensor) -> Tuple[int, int]:
-    shape = tuple(int(s) for s in x.shape)
-    if len(shape) < 1:
-        raise ValueError(f"{what}: x must be [B, ...]; got a scalar")
-    rows, per = shape[0], 1
-    for s in shape[1:]:
-        per *= s
-    return rows, per
-
-
 def rf_noise(x: Tensor, noise: Tensor, t: Tensor, x_t_out: Optional[Tensor] = None, u_out: Optional[Tensor] = None):
     """(x_t, u) = ((1 - t_r) x + t_r noise, noise - x) for x [B, ...] and one time per item, t [B] (adp_rf_noise).  t = 0
     returns x and t = 1 returns noise, bit for bit.  An output may be an input."""
-    rows, per = _rf_dims("rf_noise", x)
+    rows, per = _item_dims("rf_noise", x)
     for name, other in (("noise", noise), ("x_t_out", x_t_out), ("u_out", u_out)):
         if other is not None and other.shape != x.shape:
             raise ValueError(f"rf_noise: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
@@ -959,7 +950,7 @@ def rf_step(x: Tensor, u: Tensor, coef6: Tensor, scale: Optional[Tensor] = None,
     clip=False: x0c = x0.  clip=True: x0 is clamped to the item's scale and divided by it (scale=None: clamped to [-1, 1]);
     eps comes from the raw u.  order=1 returns x_next and has no history; order=2 returns (x_next, w) and needs `hist` (the
     previous step's w), which a row with cb = 0 does not read.  Every output may be its input."""
-    rows, per = _rf_dims("rf_step", x)
+    rows, per = _item_dims("rf_step", x)
     for name, other in (("u", u), ("hist", hist), ("out", out), ("hist_out", hist_out)):
         if other is not None and other.shape != x.shape:
             raise ValueError(f"rf_step: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
@@ -968,13 +959,7 @@ def rf_step(x: Tensor, u: Tensor, coef6: Tensor, scale: Optional[Tensor] = None,
                          f"{tuple(coef6.shape)}")
     if order not in (1, 2) or isinstance(order, bool):
         raise ValueError(f"rf_step: order must be 1 or 2; got {order!r}")
-    if not isinstance(clip, bool):
-        raise ValueError(f"rf_step: clip must be a bool; got {clip!r}")
-    if scale is not None:
-        if not clip:
-            raise ValueError("rf_step: a scale needs clip=True")
-        if scale.numel() != rows:
-            raise ValueError(f"rf_step: scale must hold one value per item ({rows}); got {scale.numel()}")
+    _check_clip("rf_step", clip, scale, rows)
     if order == 1:
         if hist is not None or hist_out is not None:
             raise ValueError("rf_step: the first-order step has no history")

@@ -19,12 +19,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import ops
-from .diffusion import (Distribution, LinearSchedule, Schedule, UniformDistribution, VDiffusion, VSampler, _on_device_of,
-                        fused_mse_loss)
-
-
-def _is_number(v) -> bool:
-    return isinstance(v, (int, float)) and not isinstance(v, bool)
+from .diffusion import (Distribution, LinearSchedule, Schedule, UniformDistribution, VDiffusion, VSampler, _Thresholded,
+                        _is_number, _on_device_of, fused_mse_loss)
 
 
 class LogitNormalDistribution(Distribution):
@@ -81,7 +77,7 @@ class RFDiffusion(VDiffusion):
             return self.loss_fn(u_pred, u_target)
 
 
-class RFSampler(VSampler):
+class RFSampler(_Thresholded, VSampler):
     """Integrates the rectified-flow ODE dx/dt = u(x, t) from the schedule's first time to its last, one net evaluation per
     step, optionally with the predicted data thresholded at every step (as `VThresholdSampler` does for the v-objective).
 
@@ -108,13 +104,12 @@ class RFSampler(VSampler):
 
     def __init__(self, net: nn.Module, schedule: Schedule = LinearSchedule(), order: int = 2,
                  dynamic_threshold: Optional[float] = None, use_graph: bool = True):
-        if isinstance(order, bool) or order not in (1, 2):
+        if not _is_number(order) or order not in (1, 2):
             raise ValueError(f"RFSampler: order must be 1 or 2; got {order!r}")
-        if dynamic_threshold is not None and not (_is_number(dynamic_threshold) and 0.0 <= dynamic_threshold <= 1.0):
-            raise ValueError(f"RFSampler: dynamic_threshold must be None or a number in [0, 1]; got {dynamic_threshold!r}")
+        threshold = self._threshold("RFSampler", dynamic_threshold, none_ok=True)
         super().__init__(net=net, schedule=schedule, use_graph=use_graph)
         self.order = order
-        self.dynamic_threshold = None if dynamic_threshold is None else float(dynamic_threshold)
+        self.dynamic_threshold = threshold
         self._strength = 1.0  # of the sampling run in progress: what `forward` hands to `_tables`
 
     def _times(self, num_steps: int, device) -> Tensor:
@@ -139,23 +134,13 @@ class RFSampler(VSampler):
     def _step_key(self) -> Tuple:
         return (self.order, self.dynamic_threshold)
 
-    def _dynamic(self) -> bool:
-        return self.dynamic_threshold is not None and self.dynamic_threshold > 0.0
-
     def _step_buffers(self, x: Tensor) -> Tuple[Tensor, ...]:
-        """(scale [B], select workspace) when the threshold is dynamic, then the history w_{i-1} for order 2.  All left
-        uninitialised: every step zeroes the workspace it uses and writes the scale before reading it, and the first step of
-        every run (cb = 0) writes the history without reading it."""
-        bufs: Tuple[Tensor, ...] = ()
-        if self._dynamic():
-            bufs = (torch.empty(x.shape[0], dtype=torch.float32, device=x.device), ops.clip_ws(x))
-        return bufs + ((torch.empty_like(x),) if self.order == 2 else ())
+        """The threshold's buffers, then the history w_{i-1} for order 2, left uninitialised: the first step of every run
+        (cb = 0) writes it without reading it."""
+        return self._threshold_buffers(x) + ((torch.empty_like(x),) if self.order == 2 else ())
 
     def _step(self, x: Tensor, v: Tensor, row: Tensor, bufs: Tuple[Tensor, ...], out: Optional[Tensor]) -> Tensor:
-        scale, hist = None, bufs
-        if self._dynamic():
-            scale, ws, hist = bufs[0], bufs[1], bufs[2:]
-            ops.clip_scale(x, self.dynamic_threshold, v=v, coef=row, min_scale=1.0, ws=ws, out=scale)
+        scale, hist = self._threshold_scale(x, v, row, bufs)
         clip = self.dynamic_threshold is not None
         if self.order == 1:
             return ops.rf_step(x, v, row, scale=scale, clip=clip, out=out)

@@ -162,7 +162,14 @@ def test_header_table_and_libraries_agree(emul):
     hip_lib = ctypes.CDLL(_C.LIB_PATH)
     for name in declared:
         assert hasattr(hip_lib, name), name
-    source = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "clip.hip")).read()
+    csrc = os.path.join(root, "audio_diffusion_pytorch_amd", "csrc")
+    source = open(os.path.join(csrc, "clip.hip")).read()
     assert '#include "adp_clip.h"' in source
-    # one helper forms x0 for the select's passes and for the step: they must round alike
-    assert source.count("clip_x0(") >= 3 and "__fmaf_rn" in source
+    # one helper forms x0 for the select's passes and for every step kernel: they must round alike.  It is defined once, on
+    # the one fused multiply-add of csrc/sampler_update.h, and no kernel source that clamps x0 spells either again
+    shared = open(os.path.join(csrc, "sampler_update.h")).read()
+    assert shared.count("float clip_x0(") == 1 and shared.count("__fmaf_rn") == 1
+    assert source.count("clip_x0(") >= 2  # the key of the passes and the step
+    for unit in ("clip.hip", "sde.hip", "rf.hip"):
+        text = open(os.path.join(csrc, unit)).read()
+        assert '#include "sampler_update.h"' in text and "clip_x0(" in text and "__fmaf_rn" not in text, unit
