@@ -40,8 +40,11 @@ class WgradDesc(Structure):
                                        "prologue", "groups", "accumulate")]
 
 
-# name -> (restype, argtypes); mirrors include/adp.h one to one
-SIGNATURES = {
+# header file of include/ -> {name: (restype, argtypes)}, each table one to one with its header: tests/test_abi.py compares
+# the names, every argument and return type and the two descriptor structs with the headers themselves
+ABI = {}
+# the base header: convs and their gradients, norms, the conditioning path, losses, sampler steps, attention, probes
+ABI["adp.h"] = {
     "adp_version": (c_int, []),
     "adp_launch_trace": (I, [I, ctypes.c_char_p, I]),
     "adp_launch_times": (I, [P, I]),
@@ -127,16 +130,15 @@ SIGNATURES = {
     "adp_probe_mfma_v": (I, [I, P, I, c_int, P]),
 }
 
-# the extension header include/adp_ar.h (autoregressive v-diffusion), one to one as well; `call` / `query` take names of
-# either table
-AR_SIGNATURES = {
+# autoregressive v-diffusion
+ABI["adp_ar.h"] = {
     "adp_arv_noise": (c_int, [P, P, P, I, I, I, I, P, P, P, P]),
     "adp_arv_step": (c_int, [P, P, P, I, I, I, I, P, P, P]),
     "adp_arv_plane": (c_int, [P, I, I, I, P, P]),
 }
 
-# the extension header include/adp_lt.h (learned-transform front end), one to one
-LT_SIGNATURES = {
+# learned-transform front end
+ABI["adp_lt.h"] = {
     "adp_lt_conv_out_len": (I, [I, I, I, I]),
     "adp_lt_convt_out_len": (I, [I, I, I, I]),
     "adp_lt_conv": (c_int, [P, P, I, I, I, I, I, I, I, I, P, P]),
@@ -145,8 +147,8 @@ LT_SIGNATURES = {
     "adp_lt_wgrad": (c_int, [P, P, I, I, I, I, I, I, I, I, I, P, P, P]),
 }
 
-# the extension header include/adp_enc.h (mel encoder: overlapping strided downsample, tanh bottleneck), one to one
-ENC_SIGNATURES = {
+# mel encoder: overlapping strided downsample, tanh bottleneck
+ABI["adp_enc.h"] = {
     "adp_enc_down_out_len": (I, [I, I]),
     "adp_enc_down_fwd": (c_int, [P, P, P, I, I, I, I, I, P, P]),
     "adp_enc_down_dgrad": (c_int, [P, P, I, I, I, I, I, P, P]),
@@ -156,8 +158,8 @@ ENC_SIGNATURES = {
     "adp_enc_tanh_bwd": (c_int, [P, P, I, P, P]),
 }
 
-# the extension header include/adp_t5.h (frozen T5 text encoder: embedding, RMS norm, token GEMM, attention), one to one
-T5_SIGNATURES = {
+# frozen T5 text encoder: embedding, RMS norm, token GEMM, attention
+ABI["adp_t5.h"] = {
     "adp_t5_embed": (c_int, [P, P, I, I, I, P, P]),
     "adp_t5_rmsnorm": (c_int, [P, P, I, I, F, P, P]),
     "adp_t5_linear_ws_bytes": (I, [I, I, I]),
@@ -165,47 +167,58 @@ T5_SIGNATURES = {
     "adp_t5_attn": (c_int, [P, P, P, P, I, I, I, I, I, P, P]),
 }
 
-# the extension header include/adp_rng.h (Philox4x32-10 normals from a device (seed, draw) row; the inpainting step that
-# draws from it), one to one
-RNG_SIGNATURES = {
+# Philox4x32-10 normals from a device (seed, draw) row; the inpainting step that draws from it
+ABI["adp_rng.h"] = {
     "adp_philox_bits": (c_int, [P, I, P, P]),
     "adp_randn": (c_int, [P, I, P, P]),
     "adp_v_inpaint_step_rng": (c_int, [P, P, P, P, P, P, I, P, P]),
 }
 
-# the extension header include/adp_clip.h (dynamic thresholding: per-item quantile scale, clip, thresholded sampler step),
-# one to one
-CLIP_SIGNATURES = {
+# dynamic thresholding: per-item quantile scale, clip, thresholded sampler step
+ABI["adp_clip.h"] = {
     "adp_clip_ws_bytes": (I, [I, I]),
     "adp_clip_scale": (c_int, [P, P, P, I, I, I, F, F, P, P, P]),
     "adp_clip_apply": (c_int, [P, P, I, I, P, P]),
     "adp_clip_step": (c_int, [P, P, P, P, P, I, P, I, I, P, P, P, P]),
 }
 
-
-# the extension header include/adp_gated.h (the gated feed-forward GEMM of the T5 v1.1 / flan-T5 encoder), one to one
-GATED_SIGNATURES = {
+# the gated feed-forward GEMM of the T5 v1.1 / flan-T5 encoder
+ABI["adp_gated.h"] = {
     "adp_gated_linear_ws_bytes": (I, [I, I, I]),
     "adp_gated_linear": (c_int, [P, P, P, I, I, I, I, P, P, P]),
 }
 
-# the extension header include/adp_sde.h (the stochastic v-sampler step on in-register Philox noise), one to one
-SDE_SIGNATURES = {
+# the stochastic v-sampler step on in-register Philox noise
+ABI["adp_sde.h"] = {
     "adp_v_step_eta": (c_int, [P, P, P, P, I, P, I, I, P, P]),
 }
 
-# the extension header include/adp_rf.h (rectified flow: the fused noising and the sampler update), one to one
-RF_SIGNATURES = {
+# rectified flow: the fused noising and the sampler update
+ABI["adp_rf.h"] = {
     "adp_rf_noise": (c_int, [P, P, P, I, I, P, P, P]),
     "adp_rf_step": (c_int, [P, P, P, P, I, I, P, I, I, P, P, P]),
 }
 
 
+# extension header -> the csrc/ file that includes and implements it (adp.h is implemented by all of them)
+HEADER_SOURCE = {"adp_ar.h": "elementwise.hip", "adp_lt.h": "lt.hip", "adp_enc.h": "encoder.hip", "adp_t5.h": "t5.hip",
+                 "adp_rng.h": "rng.hip", "adp_clip.h": "clip.hip", "adp_gated.h": "gated.hip", "adp_sde.h": "sde.hip",
+                 "adp_rf.h": "rf.hip"}
+
+# the whole C-ABI, name -> (restype, argtypes): what `_bind` binds and `call` / `call_value` / `query` resolve
+SIGNATURES = {}
+for _header, _table in ABI.items():
+    for _name in _table:
+        if _name in SIGNATURES:
+            _first = next(h for h, t in ABI.items() if _name in t)
+            raise ImportError(f"{_name} is in the tables of both {_first} and {_header}: one header declares an entry point")
+    SIGNATURES.update(_table)
+
+
 def _bind(path: str):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES, **LT_SIGNATURES, **ENC_SIGNATURES, **T5_SIGNATURES,
-                              **RNG_SIGNATURES, **CLIP_SIGNATURES, **GATED_SIGNATURES, **SDE_SIGNATURES, **RF_SIGNATURES}.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what adp.h / adp_ar.h / adp_lt.h / adp_enc.h / adp_t5.h / adp_rng.h / adp_clip.h / adp_gated.h / adp_sde.h / adp_rf.h declare
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args
     return lib
@@ -297,36 +310,32 @@ def _decode_trace(text: str) -> str:
     return " + ".join(names)
 
 
-def call(name: str, *args):
+def _profiled(name: str, args):
+    """One C-ABI call under PROFILE: its return value, after appending the call's record."""
     global _TAG
-    if PROFILE is None:
-        check(getattr(lib(), name)(*args), name)
-        return
     l = lib()
     l.adp_launch_trace(1, None, 0)      # recording on: names + a HIP event pair per launch, on the launch stream
-    check(getattr(l, name)(*args), name)
+    v = getattr(l, name)(*args)
     buf = ctypes.create_string_buffer(4096)
     l.adp_launch_trace(0, buf, 4096)
     kernels = [k for k in _decode_trace(buf.value.decode()).split(" + ") if k]
     PROFILE.append([name, kernels, _TAG or {}, None])   # the last slot receives the per-kernel times
     _TAG = None
+    return v
+
+
+def call(name: str, *args):
+    if PROFILE is None:
+        check(getattr(lib(), name)(*args), name)
+        return
+    check(_profiled(name, args), name)
 
 
 def call_value(name: str, *args) -> int:
     """`call` for entry points that launch AND return a non-negative value (negative: error code)."""
-    global _TAG
-    l = lib()
-    if PROFILE is not None:
-        l.adp_launch_trace(1, None, 0)
-    v = getattr(l, name)(*args)
-    if PROFILE is not None:
-        buf = ctypes.create_string_buffer(4096)
-        l.adp_launch_trace(0, buf, 4096)
-        kernels = [k for k in _decode_trace(buf.value.decode()).split(" + ") if k]
-        PROFILE.append([name, kernels, _TAG or {}, None])
-        _TAG = None
+    v = getattr(lib(), name)(*args) if PROFILE is None else _profiled(name, args)
     if v < 0:
-        raise RuntimeError(f"{name} failed: {ERRORS.get(v, v)} ({v})")
+        check(v, name)
     return int(v)
 
 
@@ -349,5 +358,5 @@ def profile_collect():
 def query(name: str, *args) -> int:
     v = getattr(lib(), name)(*args)
     if v < 0:
-        raise RuntimeError(f"{name} failed: {ERRORS.get(v, v)} ({v})")
+        check(v, name)
     return int(v)

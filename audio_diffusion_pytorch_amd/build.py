@@ -1,4 +1,4 @@
-"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of include/adp.h, include/adp_ar.h, include/adp_lt.h, include/adp_enc.h, include/adp_t5.h, include/adp_rng.h, include/adp_clip.h, include/adp_gated.h, include/adp_sde.h and include/adp_rf.h) in-tree with hipcc.
+"""Builds libadp_hip.so (the gfx950 kernels + C-ABI of the headers under include/) in-tree with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the resulting
 .so travels to the GPU box with the repository snapshot.  No CUDA path, no hipify, no fallback.

@@ -6,14 +6,12 @@ elementwise kernels within their roundings) and leaves every guard, offset gap a
 call; two lengths: one on the 16-byte paths (which a misplaced pointer must leave) and an odd one, whose second item starts
 off the 16-byte grid wherever the first one is."""
 import os
-import re
 
-import pytest
 import torch
 
 from audio_diffusion_pytorch_amd import _C
 from conftest import rel_err
-from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from placement import PLANS, Placer, p, single_operand_tests, whole_call_tests
 from test_multistep_sampler import KERNEL_TOL, coef_table
 from test_threshold_sampler import CLIP_TOL, LERP_TOL, clip_ref, quantile_ref, rank_of, threshold_step_ref
 
@@ -34,23 +32,23 @@ def _ws_numel(n):
 def _scale(P, n):
     (x,) = _data(n, 1)
     xd = P.inp("x", x)
-    ws, out = P.ws("ws", _ws_numel(n)), P.out("scale", (ROWS,))
+    ws, out = P.ws_numel("ws", _ws_numel(n)), P.out("scale", (ROWS,))
     lo, _, w = rank_of(Q, n)
     code = _C.lib().adp_clip_scale(p(xd), None, None, ROWS, n, lo, float(w), 0.0, p(ws), p(out), _C.stream())
     want = torch.quantile(x.abs(), Q, dim=-1)
-    return code, lambda: [("scale", ((out.cpu() - want).abs() / want).max().item(), LERP_TOL)]
+    return code, [("scale", ((out.cpu() - want).abs() / want).max().item(), "<=", LERP_TOL)]
 
 
 def _scale_fused(P, n):
     x, v = _data(n, 2)
     xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef", COEF)
-    ws, out = P.ws("ws", _ws_numel(n)), P.out("scale", (ROWS,))
+    ws, out = P.ws_numel("ws", _ws_numel(n)), P.out("scale", (ROWS,))
     lo, _, w = rank_of(Q, n)
     code = _C.lib().adp_clip_scale(p(xd), p(vd), p(cd), ROWS, n, lo, float(w), 1.0, p(ws), p(out), _C.stream())
     a0, b0 = COEF[0].double(), COEF[1].double()
     want = quantile_ref((a0 * x.double() - b0 * v.double()).abs(), Q).clamp(min=1.0)
     bound = 4 * 2.0 ** -24 * ((a0 * x.double()).abs() + (b0 * v.double()).abs()).max().item()
-    return code, lambda: [("scale", (out.cpu().double() - want).abs().max().item(), bound)]
+    return code, [("scale", (out.cpu().double() - want).abs().max().item(), "<=", bound)]
 
 
 def _apply(P, n):
@@ -60,7 +58,7 @@ def _apply(P, n):
     out = P.out("out", (ROWS, n))
     code = _C.lib().adp_clip_apply(p(xd), p(sd), ROWS, n, p(out), _C.stream())
     want = x.clamp(-scale[:, None], scale[:, None]) / scale[:, None]
-    return code, lambda: [("out", rel_err(out, want), CLIP_TOL)]
+    return code, [("out", rel_err(out, want), "<=", CLIP_TOL)]
 
 
 def _step(order, dynamic):
@@ -80,8 +78,8 @@ def _step(order, dynamic):
         code = _C.lib().adp_clip_step(p(xd), p(vd), p(hxd), p(hed), p(cd), order, p(sd), ROWS, n, p(outs[0]),
                                       p(outs[1]) if order == 2 else None, p(outs[2]) if order == 2 else None, _C.stream())
         want = threshold_step_ref(x, v, hx, he, row, scale if dynamic else None)
-        return code, lambda: [(name, rel_err(o, r), KERNEL_TOL)
-                              for name, o, r in zip(("x_out", "hist_x0_out", "hist_eps_out"), outs, want)]
+        return code, [(name, rel_err(o, r), "<=", KERNEL_TOL)
+                      for name, o, r in zip(("x_out", "hist_x0_out", "hist_eps_out"), outs, want)]
     return run
 
 
@@ -91,37 +89,9 @@ CASES = {"scale": (_scale, "adp_clip_scale"), "scale_fused": (_scale_fused, "adp
 HOST_ONLY = {"adp_clip_ws_bytes"}   # takes no pointer
 
 
-def place_and_check(dev, name, length, plan, what):
-    fn, entry = CASES[name]
-    P = Placer(dev, plan)
-    code, figures = fn(P, LENGTHS[length])
-    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
-    problems = []
-    for label, err, bound in figures():
-        print(f"{entry} ({name}) {length} [{what}] {label}: {err:.3e} (bound {bound:.3e})")
-        if not err <= bound:
-            problems.append(f"{label}: {err:.3e} > {bound:.3e}")
-    P.arena.verify()   # raises PlacementError naming the operand and the span
-    assert not problems, f"{entry} ({name}) {length}, placement {what}:\n" + "\n".join(problems)
-    return P
-
-
-@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_whole_call_placements(dev, name, length, kind):
-    place_and_check(dev, name, length, PLANS[kind], kind)
-
-
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_single_operand_placements(dev, name, length):
-    """single1: each pointer operand alone at offset 1; single2: each output alone at offset 2 (the 8-byte phase)."""
-    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
-    for operand, role in base.operands:
-        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
-        if role in OUTPUT_ROLES:
-            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+ALL = [(n, l) for n in CASES for l in LENGTHS]
+test_whole_call_placements = whole_call_tests(CASES, ALL, LENGTHS.get)
+test_single_operand_placements = single_operand_tests(CASES, ALL, LENGTHS.get)
 
 
 def test_placement_does_not_change_the_values(dev):
@@ -131,7 +101,7 @@ def test_placement_does_not_change_the_values(dev):
         P = Placer(dev, PLANS[kind])
         x, v = _data(LENGTHS["vec"], 2)
         xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef", COEF)
-        ws, scale = P.ws("ws", _ws_numel(LENGTHS["vec"])), P.out("scale", (ROWS,))
+        ws, scale = P.ws_numel("ws", _ws_numel(LENGTHS["vec"])), P.out("scale", (ROWS,))
         lo, _, w = rank_of(Q, LENGTHS["vec"])
         assert _C.lib().adp_clip_scale(p(xd), p(vd), p(cd), ROWS, LENGTHS["vec"], lo, float(w), 1.0, p(ws), p(scale),
                                        _C.stream()) == 0
@@ -143,28 +113,12 @@ def test_placement_does_not_change_the_values(dev):
 
 
 def test_every_clip_entry_point_is_placed():
-    assert {entry for _, entry in CASES.values()} | HOST_ONLY == set(_C.CLIP_SIGNATURES)
-    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES, _C.RNG_SIGNATURES):
-        assert not set(_C.CLIP_SIGNATURES) & set(other)
+    assert {entry for _, entry in CASES.values()} | HOST_ONLY == set(_C.ABI["adp_clip.h"])
 
 
-def test_header_table_and_libraries_agree(emul):
-    """include/adp_clip.h <-> _C.CLIP_SIGNATURES <-> what the built libraries export."""
-    import ctypes
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp_clip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
-    assert declared == set(_C.CLIP_SIGNATURES), declared ^ set(_C.CLIP_SIGNATURES)
-    for name in declared:
-        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
-    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
-    hip_lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip_lib, name), name
-    csrc = os.path.join(root, "audio_diffusion_pytorch_amd", "csrc")
+def test_x0_is_formed_by_one_helper():
+    csrc = os.path.join(os.path.dirname(_C.__file__), "csrc")
     source = open(os.path.join(csrc, "clip.hip")).read()
-    assert '#include "adp_clip.h"' in source
     # one helper forms x0 for the select's passes and for every step kernel: they must round alike.  It is defined once, on
     # the one fused multiply-add of csrc/sampler_update.h, and no kernel source that clamps x0 spells either again
     shared = open(os.path.join(csrc, "sampler_update.h")).read()

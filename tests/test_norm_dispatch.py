@@ -50,7 +50,7 @@ class Run:
         from audio_diffusion_pytorch_amd import _C
         self.decode = _C._decode_trace
         self.lib = ctypes.CDLL(path)
-        for name, (res, args) in _C.SIGNATURES.items():
+        for name, (res, args) in _C.ABI["adp.h"].items():
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = res, args
         self.bufs = {}

@@ -26,17 +26,13 @@ import torch.nn.functional as F
 import refs
 from audio_diffusion_pytorch_amd import _C
 from conftest import rel_err
-from placement import Arena, PlacementError, GUARD_BYTES
+from placement import (GUARD_BYTES, PLANS, AlignRefused, Arena, PlacementError, Placer, close, exact, p,
+                       place_and_check as shared_place_and_check, single)
 from refs import rnd
 
 TOL = 1e-4          # test_kernels.TOL
-ERR_ALIGN = -3
 
-# (entry point, operand) -> bytes: the alignment requirements adp.h states.  A placed call may answer ADP_ERR_ALIGN when
-# one of these operands is placed off that boundary, and only then; every other pointer takes the alignment of its type.
-ALIGN_DOCUMENTED = {("adp_conv1d", "gnb_ab"): 8}
-
-# entry points that are not placed, each with its reason; together with the table below this must equal _C.SIGNATURES
+# entry points that are not placed, each with its reason; together with the table below this must equal _C.ABI["adp.h"]
 EXCLUDED = {
     "adp_version": "no operands",
     "adp_launch_trace": "host-side introspection: writes a host string, launches nothing",
@@ -67,82 +63,6 @@ EXCLUDED = {
     "adp_probe_launch": "calibration probe: empty kernel, no operands",
     "adp_probe_chase": "calibration probe: one lane, scalar int32 loads",
 }
-
-
-def p(t):
-    return None if t is None else _C.ptr(t, t.dtype)
-
-
-class _AlignRefused(Exception):
-    pass
-
-
-class Placer:
-    """Places the operands of one call in declaration order; `plan(i, name, role)` gives operand i its offset."""
-
-    def __init__(self, dev, plan):
-        self.arena, self.plan, self.operands, self.notes = Arena(dev), plan, [], {}
-
-    def _off(self, name, role):
-        i = len(self.operands)
-        self.operands.append((name, role))
-        return self.plan(i, name, role)
-
-    def inp(self, name, data, res=False):
-        return self.arena.input(name, data, self._off(name, "res" if res else "in"))
-
-    def inout(self, name, data):
-        return self.arena.inout(name, data, self._off(name, "inout"))
-
-    def out(self, name, shape, dtype=torch.float32, written=None):
-        return self.arena.output(name, shape, self._off(name, "out"), dtype, written)
-
-    def ws(self, name, nbytes, dtype=torch.float32):
-        item = torch.empty((), dtype=dtype).element_size()
-        return self.arena.workspace(name, max(1, (nbytes + item - 1) // item), self._off(name, "ws"), dtype)
-
-    def off_boundary(self, entry):
-        """The placed operands of `entry` whose documented alignment (ALIGN_DOCUMENTED) this placement violates."""
-        return [o for (e, o), nbytes in ALIGN_DOCUMENTED.items()
-                if e == entry and o in self.arena.ops and self.arena.ops[o].view.data_ptr() % nbytes]
-
-    def ok(self, code, entry, launched=None):
-        bad = self.off_boundary(entry)
-        if bad:  # adp.h names the requirement on these operands: the call must refuse, not run a misaligned access
-            assert code == ERR_ALIGN, f"{entry} returned {code} with {bad} off the boundary adp.h documents"
-            assert not launched, f"{entry} refused the call and still launched {launched}"
-            raise _AlignRefused(f"{entry}: {bad}")
-        assert code == 0, f"{entry} returned {code} ({_C.ERRORS.get(code, '?')})"
-
-    def call(self, entry, fn):
-        """`ok(fn(), entry)` with the kernel instantiations the call launched recorded in notes["kernels"] (adp_launch_trace;
-        the names rocprofv3 reports)."""
-        lib = _C.lib()
-        lib.adp_launch_trace(1, None, 0)
-        try:
-            code = fn()
-        finally:
-            buf = ctypes.create_string_buffer(4096)
-            lib.adp_launch_trace(0, buf, 4096)
-            lib.adp_launch_times(None, 0)   # (drops the events the trace recorded)
-        names = _C._decode_trace(buf.value.decode())
-        self.notes["kernels"] = (self.notes.get("kernels", "") + " | " + names).strip(" |")
-        self.ok(code, entry, names)
-
-    def val(self, v, entry):
-        assert v > 0, f"{entry} returned {v} ({_C.ERRORS.get(v, '?')})"
-        return int(v)
-
-
-PLANS = {
-    "zero": lambda i, n, r: 0,
-    "all1": lambda i, n, r: 1,
-    "mixed": lambda i, n, r: 1 + i % 3,
-}
-
-
-def single(target, k):
-    return lambda i, n, r: k if n == target else 0
 
 
 def strided_rows(rows, cols, stride):
@@ -1117,7 +1037,7 @@ def place_and_check(dev, cid, plan, what):
     P.notes["refused"] = False
     try:
         checks = run(P)
-    except _AlignRefused:
+    except AlignRefused:
         P.arena.verify(refused=True)   # a refused call must not have touched anything, its outputs included
         P.notes["refused"] = True
         return P
@@ -1301,8 +1221,8 @@ def test_table_and_exclusions_cover_the_c_abi():
     covered = {e for c in CASES for e in c[1]}
     assert not covered & set(EXCLUDED), covered & set(EXCLUDED)
     assert all(isinstance(r, str) and r for r in EXCLUDED.values())
-    missing = set(_C.SIGNATURES) - covered - set(EXCLUDED)
-    extra = (covered | set(EXCLUDED)) - set(_C.SIGNATURES)
+    missing = set(_C.ABI["adp.h"]) - covered - set(EXCLUDED)
+    extra = (covered | set(EXCLUDED)) - set(_C.ABI["adp.h"])
     assert not missing and not extra, f"decide how to place: {sorted(missing)}; not in the C-ABI: {sorted(extra)}"
 
 
@@ -1408,6 +1328,37 @@ def test_verify_of_a_refused_call_wants_the_outputs_untouched():
     y[2] = 1.0
     with pytest.raises(PlacementError, match=r"operand 'y' .*1 element\(s\) outside the promised output written, first index 2"):
         a.verify(refused=True)
+
+
+def _stand_in(code, figures):
+    def run(P):
+        P.out("y", (4,)).fill_(1.0)   # a stand-in kernel that writes its whole output
+        return code, figures
+    return run
+
+
+def test_place_and_check_names_a_refused_call():
+    with pytest.raises(AssertionError, match=r"adp_stand_in \(case\) odd \[zero\] returned -3 \(misaligned pointer\)"):
+        shared_place_and_check("cpu", "adp_stand_in", "(case) odd", _stand_in(-3, []), PLANS["zero"], "zero")
+    assert shared_place_and_check("cpu", "adp_stand_in", "(case) odd", _stand_in(0, []), PLANS["all1"], "all1").operands == \
+        [("y", "out")]
+
+    def writes_nothing(P):
+        P.out("y", (4,))
+        return 0, []
+    with pytest.raises(PlacementError, match=r"operand 'y' \(offset 0\): 4 output element\(s\) left unwritten"):
+        shared_place_and_check("cpu", "adp_stand_in", "(case) odd", writes_nothing, PLANS["zero"], "zero")
+
+
+@pytest.mark.parametrize("figure", [("edge", 1e-4, "<", 1e-4), ("edge", 1.1e-4, "<=", 1e-4), ("edge", float("nan"), "<=", 1.0),
+                                    close("edge", torch.ones(3), torch.tensor([1.0, 1.0, 1.001]), 1e-4),
+                                    exact("edge", torch.zeros(2), torch.tensor([0.0, 2.0 ** -149]))])
+def test_place_and_check_names_a_figure_out_of_bound(figure):
+    held = ("fine", 0.0, "<", 1e-4)
+    shared_place_and_check("cpu", "adp_stand_in", "(case) odd", _stand_in(0, [held]), PLANS["zero"], "zero")
+    with pytest.raises(AssertionError, match=r"adp_stand_in \(case\) odd, placement zero:\nedge: ") as e:
+        shared_place_and_check("cpu", "adp_stand_in", "(case) odd", _stand_in(0, [held, figure]), PLANS["zero"], "zero")
+    assert "fine" not in str(e.value)
 
 
 def test_verify_respects_the_promised_elements_and_other_types():

@@ -181,23 +181,6 @@ def test_product_semantics_match_oracle_switches():
     assert set(re.findall(r"^([A-Z][A-Z0-9_]+)\s*=", block, flags=re.M)) == set(A_UNET_SEMANTICS)
 
 
-def test_c_abi_exports_every_declared_symbol():
-    """include/adp.h <-> the built libraries: every declared function is exported (no compute calls)."""
-    import ctypes
-    import re
-    from audio_diffusion_pytorch_amd import _C
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp.h")).read()
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", header)) - {"adp_conv_desc", "adp_wgrad_desc"}
-    assert declared == set(_C.SIGNATURES), declared ^ set(_C.SIGNATURES)
-    if not os.path.exists(_C.LIB_PATH):
-        pytest.skip("libadp_hip.so not built yet (run __graft_entry__.build())")
-    lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert lib.adp_version() >= 100
-
-
 def test_a_unet_checkpoint_order_loader(emul):
     """UNetV0Net.load_a_unet_state_dict: a checkpoint whose tensors come in a_unet's (recalled) NESTED registration order under
     foreign key names -- depth d + 1 between depth d's down and up items, a_unet's `blocks.N...` style names -- loads

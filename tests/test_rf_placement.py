@@ -5,15 +5,13 @@ at the zero / all1 / mixed / single1 / single2 placements.  A placed call return
 items per call; two lengths: one on the 16-byte paths (which a misplaced pointer must leave) and an odd one, whose second item
 starts off the 16-byte grid and inside a group of four."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from audio_diffusion_pytorch_amd import _C
 from conftest import rel_err
-from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from placement import PLANS, Placer, p, single_operand_tests, whole_call_tests
 from test_rf import NOISE_TOL, ROW, STEP_TOL, rf_step_ref
 
 ROWS = 2
@@ -33,7 +31,7 @@ def _noise(P, n):
     code = _C.lib().adp_rf_noise(p(xd), p(nd), p(td), ROWS, n, p(xt), p(u), _C.stream())
     tt = TIMES.double()[:, None]
     want_xt, want_u = (1 - tt) * x.double() + tt * noise.double(), noise.double() - x.double()
-    return code, lambda: [("x_t_out", rel_err(xt, want_xt), NOISE_TOL), ("u_out", rel_err(u, want_u), NOISE_TOL)]
+    return code, [("x_t_out", rel_err(xt, want_xt), "<=", NOISE_TOL), ("u_out", rel_err(u, want_u), "<=", NOISE_TOL)]
 
 
 def _step(mode, order):
@@ -53,12 +51,9 @@ def _step(mode, order):
             row[5] = 0.0
         want, want_w = rf_step_ref(x, u, hist, row, clip=mode != "plain", scale=scale)
 
-        def figures():
-            found = [("x_out", rel_err(out, want), STEP_TOL)]
-            if order == 2:
-                found.append(("hist_out", rel_err(ho, want_w), STEP_TOL))
-            return found
-
+        figures = [("x_out", rel_err(out, want), "<=", STEP_TOL)]
+        if order == 2:
+            figures.append(("hist_out", rel_err(ho, want_w), "<=", STEP_TOL))
         return code, figures
     return run
 
@@ -69,37 +64,9 @@ CASES.update({f"step-{mode}-{order}": (_step(mode, order), "adp_rf_step")
 OUTPUTS = {"adp_rf_noise": ("x_t_out", "u_out"), "adp_rf_step": ("x_out", "hist_out")}
 
 
-def place_and_check(dev, name, length, plan, what):
-    fn, entry = CASES[name]
-    P = Placer(dev, plan)
-    code, figures = fn(P, LENGTHS[length])
-    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
-    problems = []
-    for label, err, bound in figures():
-        print(f"{entry} ({name}) {length} [{what}] {label}: {err:.3e} (bound {bound:.3e})")
-        if not err <= bound:
-            problems.append(f"{label}: {err:.3e} > {bound:.3e}")
-    P.arena.verify()   # raises PlacementError naming the operand and the span
-    assert not problems, f"{entry} ({name}) {length}, placement {what}:\n" + "\n".join(problems)
-    return P
-
-
-@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_whole_call_placements(dev, name, length, kind):
-    place_and_check(dev, name, length, PLANS[kind], kind)
-
-
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", ["noise", "step-scale-2", "step-plain-1"])
-def test_single_operand_placements(dev, name, length):
-    """single1: each pointer operand alone at offset 1; single2: each output alone at offset 2 (the 8-byte phase)."""
-    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
-    for operand, role in base.operands:
-        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
-        if role in OUTPUT_ROLES:
-            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+ALL = [(n, l) for n in CASES for l in LENGTHS]
+test_whole_call_placements = whole_call_tests(CASES, ALL, LENGTHS.get)
+test_single_operand_placements = single_operand_tests(CASES, [(n, l) for n in ("noise", "step-scale-2", "step-plain-1") for l in LENGTHS], LENGTHS.get)
 
 
 @pytest.mark.parametrize("name", ["noise", "step-scale-2", "step-static-1"])
@@ -143,7 +110,7 @@ def test_noise_refusals_in_order_write_nothing(dev):
         assert L.adp_rf_noise(*a, s) == 0
     assert all(torch.equal(o.cpu(), torch.full((2, 16), 7.0)) for o in outs)
     assert L.adp_rf_noise(*args(), s) == 0 and all(torch.equal(o.cpu(), torch.zeros(2, 16)) for o in outs)
-    assert _C.RF_SIGNATURES["adp_rf_noise"] == (ctypes.c_int, [_C.P] * 3 + [_C.I] * 2 + [_C.P] * 3)
+    assert _C.ABI["adp_rf.h"]["adp_rf_noise"] == (ctypes.c_int, [_C.P] * 3 + [_C.I] * 2 + [_C.P] * 3)
 
 
 def test_step_refusals_in_order_write_nothing(dev):
@@ -185,28 +152,8 @@ def test_step_refusals_in_order_write_nothing(dev):
         assert torch.equal(out.cpu(), torch.zeros(2, 16)) and torch.equal(hout.cpu(), torch.full((2, 16), 7.0))
         out.fill_(7.0)
     assert L.adp_rf_step(*args(), s) == 0 and torch.equal(hout.cpu(), torch.zeros(2, 16))
-    assert _C.RF_SIGNATURES["adp_rf_step"] == (ctypes.c_int, [_C.P] * 4 + [_C.I, _C.I, _C.P, _C.I, _C.I, _C.P, _C.P, _C.P])
+    assert _C.ABI["adp_rf.h"]["adp_rf_step"] == (ctypes.c_int, [_C.P] * 4 + [_C.I, _C.I, _C.P, _C.I, _C.I, _C.P, _C.P, _C.P])
 
 
 def test_every_rf_entry_point_is_placed():
-    assert {entry for _, entry in CASES.values()} == set(_C.RF_SIGNATURES)
-    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES, _C.RNG_SIGNATURES,
-                  _C.CLIP_SIGNATURES, _C.GATED_SIGNATURES, _C.SDE_SIGNATURES):
-        assert not set(_C.RF_SIGNATURES) & set(other)
-
-
-def test_header_table_and_libraries_agree(emul):
-    """include/adp_rf.h <-> _C.RF_SIGNATURES <-> what the built libraries export."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp_rf.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
-    assert declared == set(_C.RF_SIGNATURES), declared ^ set(_C.RF_SIGNATURES)
-    for name in declared:
-        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
-    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
-    hip_lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip_lib, name), name
-    source = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "rf.hip")).read()
-    assert '#include "adp_rf.h"' in source
+    assert {entry for _, entry in CASES.values()} == set(_C.ABI["adp_rf.h"])

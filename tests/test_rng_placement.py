@@ -5,15 +5,11 @@ restatement (tests/test_rng.py: words exactly, normals within 1e-5 absolute, the
 leaves every guard, offset gap and input payload bit-identical.  Two lengths: one on the 16-byte paths (which a misplaced
 pointer must leave) and an odd one with a partial last group."""
 import os
-import re
 
-import pytest
 import torch
 
 from audio_diffusion_pytorch_amd import _C, ops
-from conftest import rel_err
-from placement import Arena
-from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from placement import PLANS, Placer, close, p, single_operand_tests, whole_call_tests
 from test_rng import NORMAL_TOL, STEP_TOL, reference, step_ref
 
 SEED, DRAW = 0x299F31D0A4093822, 9
@@ -21,22 +17,22 @@ LENGTHS = {"vec": 2048, "odd": 1001}
 
 
 def _row(P):
-    return P.arena.input("rng4", ops.rng_rows(SEED, [DRAW])[0], P._off("rng4", "in"))
+    return P.inp("rng4", ops.rng_rows(SEED, [DRAW])[0])
 
 
 def _bits(P, n):
     r = _row(P)
-    out = P.arena.output("out", (n,), P._off("out", "out"), dtype=torch.int32)
+    out = P.out("out", (n,), dtype=torch.int32)
     code = _C.lib().adp_philox_bits(p(r), n, p(out), _C.stream())
     want = reference(SEED, DRAW, n)[0][:n]
-    return code, lambda: [("words", float(((out.cpu().to(torch.int64) & 0xFFFFFFFF) != want).sum()), 1.0)]
+    return code, [("words", float(((out.cpu().to(torch.int64) & 0xFFFFFFFF) != want).sum()), "<", 1.0)]
 
 
 def _randn(P, n):
     r = _row(P)
     out = P.out("out", (n,))
     code = _C.lib().adp_randn(p(r), n, p(out), _C.stream())
-    return code, lambda: [("normals", (out.cpu().double() - reference(SEED, DRAW, n)[1]).abs().max().item(), NORMAL_TOL)]
+    return code, [("normals", (out.cpu().double() - reference(SEED, DRAW, n)[1]).abs().max().item(), "<", NORMAL_TOL)]
 
 
 def _step(P, n):
@@ -49,44 +45,14 @@ def _step(P, n):
     out = P.out("x_out", (n,))
     code = _C.lib().adp_v_inpaint_step_rng(p(xd), p(vd), p(sd), p(md), p(ad), p(r), n, p(out), _C.stream())
     want = step_ref(x, v, src, reference(SEED, DRAW, n)[1], mask, ab4)
-    return code, lambda: [("x_out", rel_err(out, want), STEP_TOL)]
+    return code, [close("x_out", out, want, STEP_TOL)]
 
 
 CASES = {"philox_bits": (_bits, "adp_philox_bits"), "randn": (_randn, "adp_randn"),
          "v_inpaint_step_rng": (_step, "adp_v_inpaint_step_rng")}
-
-
-def place_and_check(dev, name, length, plan, what):
-    fn, entry = CASES[name]
-    P = Placer(dev, plan)
-    code, figures = fn(P, LENGTHS[length])
-    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
-    problems = []
-    for label, err, bound in figures():
-        print(f"{entry} {length} [{what}] {label}: {err:.3e} (bound {bound:.0e})")
-        if not err < bound:
-            problems.append(f"{label}: {err:.3e} >= {bound:.0e}")
-    P.arena.verify()   # raises PlacementError naming the operand and the span
-    assert not problems, f"{entry} {length}, placement {what}:\n" + "\n".join(problems)
-    return P
-
-
-@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_whole_call_placements(dev, name, length, kind):
-    place_and_check(dev, name, length, PLANS[kind], kind)
-
-
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_single_operand_placements(dev, name, length):
-    """single1: each pointer operand alone at offset 1; single2: each output alone at offset 2 (the 8-byte phase)."""
-    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
-    for operand, role in base.operands:
-        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
-        if role in OUTPUT_ROLES:
-            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+ALL = [(n, l) for n in CASES for l in LENGTHS]
+test_whole_call_placements = whole_call_tests(CASES, ALL, LENGTHS.get)
+test_single_operand_placements = single_operand_tests(CASES, ALL, LENGTHS.get)
 
 
 def test_placement_does_not_change_the_values(dev):
@@ -102,27 +68,12 @@ def test_placement_does_not_change_the_values(dev):
 
 
 def test_every_rng_entry_point_is_placed():
-    assert {entry for _, entry in CASES.values()} == set(_C.RNG_SIGNATURES)
-    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES):
-        assert not set(_C.RNG_SIGNATURES) & set(other)
+    assert {entry for _, entry in CASES.values()} == set(_C.ABI["adp_rng.h"])
 
 
-def test_header_table_and_libraries_agree(emul):
-    """include/adp_rng.h <-> _C.RNG_SIGNATURES <-> what the built libraries export."""
-    import ctypes
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp_rng.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
-    assert declared == set(_C.RNG_SIGNATURES), declared ^ set(_C.RNG_SIGNATURES)
-    for name in declared:
-        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
-    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
-    hip_lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip_lib, name), name
-    source = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "rng.hip")).read()
-    assert '#include "adp_rng.h"' in source
-    assert '#include "inpaint_blend.h"' in source   # the blend is adp_v_inpaint_step's, not a restatement of it
-    elementwise = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "elementwise.hip")).read()
+def test_the_inpainting_blend_is_stated_once():
+    """The blend is adp_v_inpaint_step's, not a restatement of it."""
+    csrc = os.path.join(os.path.dirname(_C.__file__), "csrc")
+    assert '#include "inpaint_blend.h"' in open(os.path.join(csrc, "rng.hip")).read()
+    elementwise = open(os.path.join(csrc, "elementwise.hip")).read()
     assert '#include "inpaint_blend.h"' in elementwise and "adp_v_inpaint_blend(" in elementwise

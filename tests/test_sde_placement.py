@@ -7,14 +7,12 @@ two lengths: one on the 16-byte paths (which a misplaced pointer must leave) and
 16-byte grid and inside a group of four."""
 import ctypes
 import os
-import re
 
-import pytest
 import torch
 
 from audio_diffusion_pytorch_amd import _C, ops
 from conftest import rel_err
-from test_encoder_placement import OUTPUT_ROLES, PLANS, Placer, p
+from placement import PLANS, Placer, p, single_operand_tests, whole_call_tests
 from test_rng import NORMAL_TOL, reference
 from test_stochastic_sampler import ROW, STEP_TOL, step_ref
 
@@ -36,50 +34,22 @@ def _step(mode):
         x, v = _data(n)
         scale = torch.tensor([1.0, 1.75]) if mode == "scale" else None
         xd, vd, cd = P.inp("x", x), P.inp("v", v), P.inp("coef5", ROW)
-        rd = P.arena.input("rng4", ops.rng_rows(SEED, [DRAW])[0], P._off("rng4", "in"))
+        rd = P.inp("rng4", ops.rng_rows(SEED, [DRAW])[0])
         sd = P.inp("scale", scale) if scale is not None else None
         out = P.out("x_out", (ROWS, n))
         code = _C.lib().adp_v_step_eta(p(xd), p(vd), p(cd), p(rd), int(mode != "plain"), p(sd), ROWS, n, p(out), _C.stream())
         z = reference(SEED, DRAW, ROWS * n)[1][:ROWS * n].view(ROWS, n)
         want = step_ref(x, v, ROW, z, clip=mode != "plain", scale=scale)
-        return code, lambda: [("x_out", rel_err(out, want), TOL)]
+        return code, [("x_out", rel_err(out, want), "<=", TOL)]
     return run
 
 
 CASES = {mode: (_step(mode), "adp_v_step_eta") for mode in ("plain", "static", "scale")}
 
 
-def place_and_check(dev, name, length, plan, what):
-    fn, entry = CASES[name]
-    P = Placer(dev, plan)
-    code, figures = fn(P, LENGTHS[length])
-    assert code == 0, f"{entry} {length} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
-    problems = []
-    for label, err, bound in figures():
-        print(f"{entry} ({name}) {length} [{what}] {label}: {err:.3e} (bound {bound:.3e})")
-        if not err <= bound:
-            problems.append(f"{label}: {err:.3e} > {bound:.3e}")
-    P.arena.verify()   # raises PlacementError naming the operand and the span
-    assert not problems, f"{entry} ({name}) {length}, placement {what}:\n" + "\n".join(problems)
-    return P
-
-
-@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_whole_call_placements(dev, name, length, kind):
-    place_and_check(dev, name, length, PLANS[kind], kind)
-
-
-@pytest.mark.parametrize("length", list(LENGTHS))
-@pytest.mark.parametrize("name", list(CASES))
-def test_single_operand_placements(dev, name, length):
-    """single1: each pointer operand alone at offset 1; single2: the output alone at offset 2 (the 8-byte phase)."""
-    base = place_and_check(dev, name, length, PLANS["zero"], "zero")
-    for operand, role in base.operands:
-        place_and_check(dev, name, length, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
-        if role in OUTPUT_ROLES:
-            place_and_check(dev, name, length, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+ALL = [(n, l) for n in CASES for l in LENGTHS]
+test_whole_call_placements = whole_call_tests(CASES, ALL, LENGTHS.get)
+test_single_operand_placements = single_operand_tests(CASES, ALL, LENGTHS.get)
 
 
 def test_placement_does_not_change_the_values(dev):
@@ -128,33 +98,18 @@ def test_refusals_in_order_write_nothing(dev):
     a = args()
     a[3] = None                          # cz = 0: no row needed
     assert L.adp_v_step_eta(*a, s) == 0 and torch.equal(out.cpu(), torch.zeros(2, 16))
-    assert _C.SDE_SIGNATURES["adp_v_step_eta"] == (ctypes.c_int, [_C.P] * 4 + [_C.I, _C.P, _C.I, _C.I, _C.P, _C.P])
+    assert _C.ABI["adp_sde.h"]["adp_v_step_eta"] == (ctypes.c_int, [_C.P] * 4 + [_C.I, _C.P, _C.I, _C.I, _C.P, _C.P])
 
 
 def test_every_sde_entry_point_is_placed():
-    assert {entry for _, entry in CASES.values()} == set(_C.SDE_SIGNATURES)
-    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES, _C.T5_SIGNATURES, _C.RNG_SIGNATURES,
-                  _C.CLIP_SIGNATURES, _C.GATED_SIGNATURES):
-        assert not set(_C.SDE_SIGNATURES) & set(other)
+    assert {entry for _, entry in CASES.values()} == set(_C.ABI["adp_sde.h"])
 
 
-def test_header_table_and_libraries_agree(emul):
-    """include/adp_sde.h <-> _C.SDE_SIGNATURES <-> what the built libraries export."""
+def test_one_philox_generator():
+    """rng.hip draws from the same header as sde.hip and states no Philox round of its own."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp_sde.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
-    assert declared == set(_C.SDE_SIGNATURES), declared ^ set(_C.SDE_SIGNATURES)
-    for name in declared:
-        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
-    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
-    hip_lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip_lib, name), name
     csrc = os.path.join(root, "audio_diffusion_pytorch_amd", "csrc")
-    source = open(os.path.join(csrc, "sde.hip")).read()
-    assert '#include "adp_sde.h"' in source and '#include "philox.h"' in source
-    # one generator: rng.hip draws from the same header and states no Philox round of its own
-    rng = open(os.path.join(csrc, "rng.hip")).read()
-    assert '#include "philox.h"' in rng and "PHILOX_M0" not in rng and "PHILOX_M0" not in source
+    source, rng = open(os.path.join(csrc, "sde.hip")).read(), open(os.path.join(csrc, "rng.hip")).read()
+    assert '#include "philox.h"' in source and '#include "philox.h"' in rng
+    assert "PHILOX_M0" not in rng and "PHILOX_M0" not in source
     assert "adp_v_step_eta" not in open(os.path.join(root, "include", "adp_rng.h")).read()

@@ -5,22 +5,16 @@ int32 buckets, uint8 mask bytes).  A placed call returns ADP_OK, agrees with the
 bound (1e-4, tests/test_t5.py) and leaves every guard, offset gap and input payload bit-identical.  Two geometries: one whose
 rows are whole 16-byte groups and an odd one."""
 import functools
-import os
-import re
 
-import pytest
 import torch
 
 from audio_diffusion_pytorch_amd import _C
 from audio_diffusion_pytorch_amd.text import relative_position_buckets
-from conftest import rel_err
-from placement import Arena
-from test_encoder_placement import PLANS, Placer, p
+from placement import close, p, single_operand_tests, whole_call_tests
 from test_t5 import TOL, prefix_mask
 
 import t5_ref
 
-OUTPUT_ROLES = ("out", "inout")
 # T tokens = B x m, d model features, N outputs of the GEMM, V table rows, H heads of dk, nb buckets; "split": a k sum long
 # enough to go through the workspace
 GEOMS = {"vec16": dict(B=2, m=8, d=16, N=8, V=12, H=2, dk=8, nb=8, K=16),
@@ -60,14 +54,14 @@ def _embed(P, d):
     ids, table = P.inp("ids", d["ids"]), P.inp("table", d["table"])
     out = P.out("out", d["emb"].shape)
     code = _C.lib().adp_t5_embed(p(ids), p(table), d["T"], d["V"], d["d"], p(out), _C.stream())
-    return code, [("out", out, d["emb"])]
+    return code, [close("out", out, d["emb"], TOL)]
 
 
 def _rmsnorm(P, d):
     x, g = P.inp("x", d["x"]), P.inp("g", d["gain"])
     y = P.out("y", d["norm"].shape)
     code = _C.lib().adp_t5_rmsnorm(p(x), p(g), d["T"], d["d"], 1e-6, p(y), _C.stream())
-    return code, [("y", y, d["norm"])]
+    return code, [close("y", y, d["norm"], TOL)]
 
 
 def _linear(P, d):
@@ -75,9 +69,9 @@ def _linear(P, d):
     y = P.out("y", d["lin"].shape)
     nbytes = _C.lib().adp_t5_linear_ws_bytes(d["T"], d["K"], d["N"])
     assert nbytes >= 0 and nbytes % 4 == 0 and (nbytes > 0) == (d["K"] > 128)
-    ws = P.ws("ws", nbytes // 4) if nbytes else None
+    ws = P.ws_numel("ws", nbytes // 4) if nbytes else None
     code = _C.lib().adp_t5_linear(p(x), p(w), p(res), d["T"], d["K"], d["N"], 1, p(y), p(ws), _C.stream())
-    return code, [("y", y, d["lin"])]
+    return code, [close("y", y, d["lin"], TOL)]
 
 
 def _attn(P, d):
@@ -86,10 +80,10 @@ def _attn(P, d):
     out = P.out("out", d["attn"].shape)
     code = _C.lib().adp_t5_attn(p(qkv), p(rel), p(bucket), p(mask), d["B"], d["H"], d["dk"], d["m"], d["nb"], p(out),
                                 _C.stream())
-    return code, [("out", out, d["attn"])]
+    return code, [close("out", out, d["attn"], TOL)]
 
 
-# case -> (placing function, the entry point it places); with QUERIES they must cover _C.T5_SIGNATURES
+# case -> (placing function, the entry point it places); with QUERIES they must cover _C.ABI["adp_t5.h"]
 CASES = {
     "embed": (_embed, "adp_t5_embed"),
     "rmsnorm": (_rmsnorm, "adp_t5_rmsnorm"),
@@ -99,69 +93,14 @@ CASES = {
 QUERIES = {"adp_t5_linear_ws_bytes": "size query, integers only"}
 
 
-def place_and_check(dev, name, geom, plan, what):
-    fn, entry = CASES[name]
-    P = Placer(dev, plan)
-    code, close = fn(P, case(geom))
-    assert code == 0, f"{entry} {geom} [{what}] returned {code} ({_C.ERRORS.get(code, '?')})"
-    problems = []
-    for label, got, want in close:
-        err = rel_err(got, want)
-        print(f"{entry} {name} {geom} [{what}] {label}: rel err {err:.3e} (bound {TOL:.0e})")
-        if not err < TOL:
-            problems.append(f"{label}: rel err {err:.3e} >= {TOL:.0e}")
-    P.arena.verify()   # raises PlacementError naming the operand and the span
-    assert not problems, f"{entry} {geom}, placement {what}:\n" + "\n".join(problems)
-    return P
-
-
 def _geoms(name):
     return [g for g in GEOMS if g != "split" or name == "linear"]
 
 
 ALL = [(n, g) for n in CASES for g in _geoms(n)]
-
-
-@pytest.mark.parametrize("kind", ["zero", "all1", "mixed"])
-@pytest.mark.parametrize("name,geom", ALL)
-def test_whole_call_placements(dev, name, geom, kind):
-    place_and_check(dev, name, geom, PLANS[kind], kind)
-
-
-@pytest.mark.parametrize("name,geom", ALL)
-def test_single_operand_placements(dev, name, geom):
-    """single1: each pointer operand alone at offset 1; single2: each output alone at offset 2 (the 8-byte phase)."""
-    base = place_and_check(dev, name, geom, PLANS["zero"], "zero")
-    for operand, role in base.operands:
-        place_and_check(dev, name, geom, lambda i, n, r, t=operand: 1 if n == t else 0, f"{operand}@1")
-        if role in OUTPUT_ROLES:
-            place_and_check(dev, name, geom, lambda i, n, r, t=operand: 2 if n == t else 0, f"{operand}@2")
+test_whole_call_placements = whole_call_tests(CASES, ALL, case)
+test_single_operand_placements = single_operand_tests(CASES, ALL, case)
 
 
 def test_every_t5_entry_point_is_placed():
-    assert {entry for _, entry in CASES.values()} | set(QUERIES) == set(_C.T5_SIGNATURES)
-    for other in (_C.SIGNATURES, _C.AR_SIGNATURES, _C.LT_SIGNATURES, _C.ENC_SIGNATURES):
-        assert not set(_C.T5_SIGNATURES) & set(other)
-
-
-def test_header_table_and_libraries_agree(emul):
-    """include/adp_t5.h <-> _C.T5_SIGNATURES <-> what the built libraries export."""
-    import ctypes
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "adp_t5.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)   # (the comments name other functions)
-    declared = set(re.findall(r"\b(adp_[a-z0-9_]+)\s*\(", code))
-    assert declared == set(_C.T5_SIGNATURES), declared ^ set(_C.T5_SIGNATURES)
-    for name in declared:
-        assert hasattr(_C.lib(), name), name            # the emulated build of the same sources
-    assert os.path.exists(_C.LIB_PATH), "libadp_hip.so is not built (run __graft_entry__.build())"
-    hip_lib = ctypes.CDLL(_C.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip_lib, name), name
-    # the library's dynamic symbol table holds exactly the adp_t5_* names the header declares
-    syms = subprocess.run(["nm", "-D", "--defined-only", _C.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in syms.splitlines() if ln.split() and ln.split()[-1].startswith("adp_t5_")}
-    assert exported == declared, exported ^ declared
-    source = open(os.path.join(root, "audio_diffusion_pytorch_amd", "csrc", "t5.hip")).read()
-    assert '#include "adp_t5.h"' in source
+    assert {entry for _, entry in CASES.values()} | set(QUERIES) == set(_C.ABI["adp_t5.h"])

@@ -17,7 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from audio_diffusion_pytorch_amd._C import AR_SIGNATURES, SIGNATURES, ConvDesc, WgradDesc  # noqa: E402
+from audio_diffusion_pytorch_amd._C import ABI, ConvDesc, WgradDesc  # noqa: E402
 
 KNOBS = [
     {},
@@ -35,7 +35,7 @@ A = 0x7f0000000000  # fabricated, 4 KiB-aligned operand addresses, 16 MiB apart
 
 def bind(path):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **AR_SIGNATURES}.items():
+    for name, (res, args) in {**ABI["adp.h"], **ABI["adp_ar.h"]}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
