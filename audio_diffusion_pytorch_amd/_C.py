@@ -199,11 +199,17 @@ ABI["adp_rf.h"] = {
     "adp_rf_step": (c_int, [P, P, P, P, I, I, P, I, I, P, P, P]),
 }
 
+# Karras (EDM) diffusion: the fused noising and the sampler update on the scaled state
+ABI["adp_edm.h"] = {
+    "adp_edm_noise": (c_int, [P, P, P, F, I, I, P, P, P]),
+    "adp_edm_step": (c_int, [P, P, P, P, P, I, I, P, I, I, P, P, P]),
+}
+
 
 # extension header -> the csrc/ file that includes and implements it (adp.h is implemented by all of them)
 HEADER_SOURCE = {"adp_ar.h": "elementwise.hip", "adp_lt.h": "lt.hip", "adp_enc.h": "encoder.hip", "adp_t5.h": "t5.hip",
                  "adp_rng.h": "rng.hip", "adp_clip.h": "clip.hip", "adp_gated.h": "gated.hip", "adp_sde.h": "sde.hip",
-                 "adp_rf.h": "rf.hip"}
+                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip"}
 
 # the whole C-ABI, name -> (restype, argtypes): what `_bind` binds and `call` / `call_value` / `query` resolve
 SIGNATURES = {}

@@ -15,6 +15,7 @@ from .diffusion import (
     VStochasticSampler,
     VSampler,
 )
+from .edm import KarrasSchedule, KDiffusion, KSampler, LogNormalDistribution
 from .losses import MultiResolutionSTFTLoss, STFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
 from .optim import AdamW
@@ -54,4 +55,5 @@ __all__ = [
     "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
     "RFDiffusion", "RFSampler", "LogitNormalDistribution",
+    "KDiffusion", "KSampler", "KarrasSchedule", "LogNormalDistribution",
 ]

@@ -1,0 +1,215 @@
+// Karras (EDM) diffusion (include/adp_edm.h): the fused noising of the training step and the sampler update on the scaled
+// state xs = c_in(sigma) x.
+//   adp_edm_noise : x_in = c_in x + (c_in sigma) n ; target = (sigma / (sd r)) x - (sd / r) n              2 reads, 2 writes
+//   adp_edm_step  : xs_out = c1 clip(a0 xs - b0 F) + d1 (e0 xs + f0 F) [+ cb (x0c - hist)] [+ s1 z]        2 reads, 1 write
+//                                                                                                 (order 2: 3 reads, 2 writes)
+// Both are bandwidth-bound elementwise passes of rf_step_kernel's shape (rf.hip): one thread owns one group of four elements
+// per pass, in a grid-stride loop over the groups; 16-byte accesses where every tensor operand allows them, single elements
+// otherwise.  The per-item values (sigma, scale) are found by one 64-bit division per group and a walk over the item
+// boundaries inside it (item_values4); the noise z is formed in registers from the row of include/adp_rng.h, one Philox
+// call and two Box-Muller pairs per group (philox.h), as in sde.hip.  No LDS, no atomics, no cross-lane traffic; ordinary
+// vector or single-element stores only.  The arithmetic of x0 and its clamps, the walk and the grid are
+// csrc/sampler_update.h's, shared with clip.hip, sde.hip and rf.hip.
+#include "adp_rt.h"
+#include "adp.h"
+#include "adp_edm.h"
+#include "philox.h"
+#include "sampler_update.h"
+
+namespace {
+
+using namespace philox;
+using namespace upd;
+
+// ---- noising.  The four per-item coefficients by the sequence of the header: one product, one fused multiply-add, one
+// square root and four divisions, each correctly rounded (the product build keeps hipcc's default, correctly rounded
+// float32 division and square root), so the emulated build forms the same bits.
+struct EdmNoiseCoef {
+  float c_in, c_n, t_x, t_n;
+};
+
+__device__ __forceinline__ EdmNoiseCoef edm_noise_coef(float sigma, float sd) {
+  const float r = sqrtf(fma_rn(sigma, sigma, sd * sd));
+  EdmNoiseCoef c;
+  c.c_in = 1.0f / r;
+  c.c_n = sigma / r;
+  c.t_x = c.c_n / sd;
+  c.t_n = sd / r;
+  return c;
+}
+
+struct EdmNoised {
+  float x_in, target;
+};
+
+__device__ __forceinline__ EdmNoised edm_noise_elem(const EdmNoiseCoef& c, float xv, float nv) {
+  EdmNoised r;
+  r.x_in = fma_rn(c.c_in, xv, c.c_n * nv);
+  r.target = fma_rn(c.t_x, xv, -(c.t_n * nv));
+  return r;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void edm_noise_kernel(const float* x, const float* noise, const float* sigma, float sd,
+                                                        int64_t n, int64_t per, float* xi, float* tg) {
+  const int64_t groups = groups4(n);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t e = 4 * g;
+    float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    item_values4(sigma, e, n, per, sv);
+    // the coefficients are a function of the item's sigma alone: formed for the group's first element and again only where
+    // the walk met another value (a NaN sigma compares unequal and is formed again: the same NaN coefficients)
+    EdmNoiseCoef c[4];
+    c[0] = edm_noise_coef(sv[0], sd);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) c[k] = sv[k] == sv[k - 1] ? c[k - 1] : edm_noise_coef(sv[k], sd);
+    if (VEC && e + 4 <= n) {
+      const f32x4 xv = *(const f32x4*)(x + e), nv = *(const f32x4*)(noise + e);
+      f32x4 a, b;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const EdmNoised r = edm_noise_elem(c[k], xv[k], nv[k]);
+        a[k] = r.x_in;
+        b[k] = r.target;
+      }
+      *(f32x4*)(xi + e) = a;
+      *(f32x4*)(tg + e) = b;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < n) {
+          const EdmNoised r = edm_noise_elem(c[k], x[e + k], noise[e + k]);  // (both read before either store: aliasing)
+          xi[e + k] = r.x_in;
+          tg[e + k] = r.target;
+        }
+    }
+  }
+}
+
+// ---- the sampler update
+struct EdmCoef {
+  float a0, b0, e0, f0, c1, d1, s1, cb;
+};
+
+struct EdmStepped {
+  float xn, x0c;
+};
+
+// One element, by the rounding sequence of the header.  x0 and its clamps are sampler_update.h's clip_x0 and clipped, the
+// ones clip.hip's select ranks and adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale
+// stays NaN.
+template <int CLIP, int ORDER>
+__device__ __forceinline__ EdmStepped edm_step_elem(const EdmCoef& c, float s, float xv, float fv, float hv, float z,
+                                                    bool multi, bool noisy) {
+  const float x0 = clip_x0(c.a0, xv, c.b0, fv);
+  const float nh = fma_rn(c.e0, xv, c.f0 * fv);
+  EdmStepped r;
+  r.x0c = clipped<CLIP>(x0, s);
+  r.xn = fma_rn(c.c1, r.x0c, c.d1 * nh);
+  if (ORDER == 2 && multi) r.xn = fma_rn(c.cb, r.x0c - hv, r.xn);
+  if (noisy) r.xn = fma_rn(c.s1, z, r.xn);
+  return r;
+}
+
+// VEC: xs, f, xo (and hist, ho for ORDER 2) are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per].
+template <int CLIP, int ORDER, bool VEC>
+__global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const float* f, const float* hist,
+                                                       const float* coef8, const uint32_t* rng4, const float* scale,
+                                                       int64_t n, int64_t per, float* xo, float* ho) {
+  const EdmCoef c{coef8[0], coef8[1], coef8[2], coef8[3], coef8[4], coef8[5], coef8[6], coef8[7]};
+  const bool multi = ORDER == 2 && c.cb != 0.0f;  // (the same branches in every lane of the launch)
+  const bool noisy = c.s1 != 0.0f;
+  RngRow row{0u, 0u, 0u};
+  if (noisy && rng4) row = rng_row(rng4);
+  const float nan = __uint_as_float(0x7FC00000u);
+  const int64_t groups = groups4(n);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t e = 4 * g;
+    f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (noisy) {
+      if (rng4) {
+        z = rng_normal4(row, g);
+      } else {
+        const f32x4 z_nan = {nan, nan, nan, nan};  // noise asked for without a row: loud, and nothing is dereferenced
+        z = z_nan;
+      }
+    }
+    float s[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    if (CLIP == CLIP_SCALE) item_values4(scale, e, n, per, s);
+    if (VEC && e + 4 <= n) {
+      const f32x4 xv = *(const f32x4*)(x + e), fv = *(const f32x4*)(f + e);
+      f32x4 hv = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (multi) hv = *(const f32x4*)(hist + e);
+      f32x4 o, w;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], xv[k], fv[k], hv[k], z[k], multi, noisy);
+        o[k] = r.xn;
+        w[k] = r.x0c;
+      }
+      *(f32x4*)(xo + e) = o;
+      if (ORDER == 2) *(f32x4*)(ho + e) = w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < n) {
+          const float hv = multi ? hist[e + k] : 0.0f;
+          const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], x[e + k], f[e + k], hv, z[k], multi, noisy);
+          xo[e + k] = r.xn;
+          if (ORDER == 2) ho[e + k] = r.x0c;
+        }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int adp_edm_noise(const float* x, const float* noise, const float* sigma, float sigma_data, int64_t rows,
+                             int64_t per, float* x_in_out, float* target_out, void* stream) {
+  if (!x || !noise || !sigma || !x_in_out || !target_out) return ADP_ERR_NULL;
+  if (rows < 0 || per < 0 || !(sigma_data > 0.0f)) return ADP_ERR_SHAPE;
+  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
+  if (misaligned(x, 4) || misaligned(noise, 4) || misaligned(sigma, 4) || misaligned(x_in_out, 4) ||
+      misaligned(target_out, 4))
+    return ADP_ERR_ALIGN;
+  const int64_t n = rows * per;
+  if (n == 0) return ADP_OK;
+  const bool vec = !misaligned(x, 16) && !misaligned(noise, 16) && !misaligned(x_in_out, 16) && !misaligned(target_out, 16);
+  with_flag(vec, [&](auto VEC) {
+    ADP_LAUNCH((edm_noise_kernel<VEC()>), dim3(grid4(n)), dim3(256), stream, x, noise, sigma, sigma_data, n, per, x_in_out,
+               target_out);
+  });
+  return ADP_LAUNCH_OK();
+}
+
+extern "C" int adp_edm_step(const float* xs, const float* f, const float* hist, const float* coef8, const uint32_t* rng4,
+                            int64_t order, int64_t clip, const float* scale, int64_t rows, int64_t per, float* xs_out,
+                            float* hist_out, void* stream) {
+  if (!xs || !f || !coef8 || !xs_out) return ADP_ERR_NULL;
+  if (order == 2 && (!hist || !hist_out)) return ADP_ERR_NULL;
+  if (rows < 0 || per < 0 || (order != 1 && order != 2) || (clip != 0 && clip != 1) || (clip == 0 && scale))
+    return ADP_ERR_SHAPE;
+  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
+  if (misaligned(xs, 4) || misaligned(f, 4) || misaligned(coef8, 4) || misaligned(xs_out, 4) ||
+      (rng4 && misaligned(rng4, 4)) || (scale && misaligned(scale, 4)) ||
+      (order == 2 && (misaligned(hist, 4) || misaligned(hist_out, 4))))
+    return ADP_ERR_ALIGN;
+  const int64_t n = rows * per;
+  if (n == 0) return ADP_OK;
+  bool vec = !misaligned(xs, 16) && !misaligned(f, 16) && !misaligned(xs_out, 16);
+  if (order == 2) {
+    vec = vec && !misaligned(hist, 16) && !misaligned(hist_out, 16);
+  } else {  // (the first-order kernels take no history)
+    hist = nullptr;
+    hist_out = nullptr;
+  }
+  with_clip(clip, scale, [&](auto CLIP) {
+    with_flag(order == 2, [&](auto ORDER2) {
+      with_flag(vec, [&](auto VEC) {
+        ADP_LAUNCH((edm_step_kernel<CLIP(), ORDER2() ? 2 : 1, VEC()>), dim3(grid4(n)), dim3(256), stream, xs, f, hist, coef8,
+                   rng4, scale, n, per, xs_out, hist_out);
+      });
+    });
+  });
+  return ADP_LAUNCH_OK();
+}

@@ -4,7 +4,7 @@
 `VMultistepSampler` (second-order two-step integrator, one net evaluation per step) is this package's own, and so is
 `VThresholdSampler`, which puts the reference's `clip` (dynamic thresholding, diffusion.py:36-54) inside the sampling loop,
 and `VStochasticSampler` (DDIM with eta > 0 on noise formed inside the update kernel).  Rectified flow (`RFDiffusion`,
-`RFSampler`) builds on these classes from rf.py.
+`RFSampler`) builds on these classes from rf.py, Karras (EDM) diffusion (`KDiffusion`, `KSampler`) from edm.py.
 
 Differences from the reference are structural, not numerical:
   * noising (x_noisy, v_target) is one fused kernel (2 reads, 2 writes) instead of ~6 elementwise ops;
@@ -452,7 +452,7 @@ class VMultistepSampler(VSampler):
 
 
 class _Thresholded:
-    """The dynamic-threshold glue of `VThresholdSampler`, `VStochasticSampler` and `rf.RFSampler` (mixed into a `VSampler`
+    """The dynamic-threshold glue of `VThresholdSampler`, `VStochasticSampler`, `rf.RFSampler` and `edm.KSampler` (mixed into a `VSampler`
     that sets `self.dynamic_threshold`): None = no clipping, 0.0 = the static clamp to [-1, 1], q in (0, 1] = the per-item
     quantile scale of include/adp_clip.h, selected in front of the update kernel from the step's own (x, v, coefficient row)."""
 

@@ -974,6 +974,116 @@ def rf_step(x: Tensor, u: Tensor, coef6: Tensor, scale: Optional[Tensor] = None,
     return out if order == 1 else (out, hist_out)
 
 
+# ---- include/adp_edm.h: Karras (EDM) diffusion (the fused noising and the sampler update on the scaled state)
+
+def _check_sigma_data(what: str, sigma_data) -> float:
+    if isinstance(sigma_data, bool) or not isinstance(sigma_data, (int, float)) or not sigma_data > 0.0:
+        raise ValueError(f"{what}: sigma_data must be a positive number; got {sigma_data!r}")
+    return float(sigma_data)
+
+
+def edm_noise(x: Tensor, noise: Tensor, sigma: Tensor, sigma_data: float = 0.5, x_in_out: Optional[Tensor] = None,
+              target_out: Optional[Tensor] = None):
+    """(x_in, target) = (c_in x + c_in sigma_r noise, (sigma_r / (sd r)) x - (sd / r) noise) for x [B, ...] and one sigma per
+    item, sigma [B] (adp_edm_noise): what the preconditioned net reads and what it is trained towards.  x_in is the sampler's
+    scaled state of x + sigma_r noise.  An output may be an input."""
+    rows, per = _item_dims("edm_noise", x)
+    for name, other in (("noise", noise), ("x_in_out", x_in_out), ("target_out", target_out)):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"edm_noise: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    if sigma.dtype != torch.float32 or sigma.numel() != rows:
+        raise ValueError(f"edm_noise: sigma holds one float32 value per item ({rows}); got {sigma.dtype} {tuple(sigma.shape)}")
+    sd = _check_sigma_data("edm_noise", sigma_data)
+    if x_in_out is None:
+        x_in_out = torch.empty_like(x)
+    if target_out is None:
+        target_out = torch.empty_like(x)
+    _C.call("adp_edm_noise", ptr(x), ptr(noise), ptr(sigma), sd, rows, per, ptr(x_in_out), ptr(target_out), _C.stream())
+    return x_in_out, target_out
+
+
+def edm_table(sigmas, sigma_data: float = 0.5, order: int = 2, eta: float = 0.0) -> Tensor:
+    """The sampler's coefficient rows [N, 8] = (a0, b0, e0, f0, c1, d1, s1, cb) for the noise levels sigma_0 .. sigma_N
+    (include/adp_edm.h), float32 on the CPU: formed in float64 and rounded once.  With sd = sigma_data, r = sqrt(s^2 + sd^2):
+
+        a0 = sd^2 / r_i    b0 = -s_i sd / r_i    e0 = s_i / r_i    f0 = -sd / r_i
+        g = 1 / r_{i+1} (1 on the last step)     c1 = g            d1 = g s_down     s1 = g s_up
+        s_up = min(s_{i+1}, eta sqrt(s_{i+1}^2 (s_i^2 - s_{i+1}^2) / s_i^2))         s_down = sqrt(s_{i+1}^2 - s_up^2)
+        cb_i = g (1 - s_{i+1} / s_i) h_i / (2 h_{i-1}),  h_i = ln(s_i / s_{i+1})     for order 2, i > 0 and s_{i+1} > 0, else 0
+
+    cb is DPM-Solver++(2M)'s weight of (D_i - D_{i-1}): the step in -ln(sigma) over twice the previous one.  The sigmas must
+    fall strictly; only the last one may be 0."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"edm_table: order must be 1 or 2; got {order!r}")
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0.0 <= eta <= 1.0:
+        raise ValueError(f"edm_table: eta must be a number in [0, 1]; got {eta!r}")
+    if eta > 0.0 and order == 2:
+        raise ValueError("edm_table: eta > 0 needs order=1 (there is no second-order stochastic update)")
+    sd = _check_sigma_data("edm_table", sigma_data)
+    s = torch.as_tensor(sigmas).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    if s.numel() < 1:
+        raise ValueError("edm_table: sigmas must hold at least sigma_0")
+    n = s.numel() - 1
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError("edm_table: every sigma must be finite")
+    if bool((s[:-1] <= 0).any()):
+        raise ValueError(f"edm_table: sigma_{int((s[:-1] <= 0).nonzero()[0])} is not positive; only the last sigma may be 0")
+    if s[-1] < 0:
+        raise ValueError(f"edm_table: the last sigma must not be negative; got {s[-1].item()}")
+    if bool((s[1:] >= s[:-1]).any()):
+        raise ValueError(f"edm_table: the sigmas must fall strictly; sigma_{int((s[1:] >= s[:-1]).nonzero()[0]) + 1} does not")
+    s0, s1 = s[:-1], s[1:]
+    r0 = torch.sqrt(s0 * s0 + sd * sd)
+    g = 1.0 / torch.sqrt(s1 * s1 + sd * sd)
+    if n > 0:
+        g[-1] = 1.0
+    up = torch.minimum(s1, eta * torch.sqrt(s1 * s1 * (s0 * s0 - s1 * s1) / (s0 * s0)))
+    down = torch.sqrt((s1 * s1 - up * up).clamp_min(0.0))
+    cb = torch.zeros(n, dtype=torch.float64)
+    if order == 2 and n > 1:
+        multi = s1[1:] > 0
+        h = torch.log(s0[1:] / torch.where(multi, s1[1:], s0[1:]))     # (h_i, 0 where the step ends at sigma = 0)
+        h_last = torch.log(s0[:-1] / s0[1:])
+        cb[1:] = torch.where(multi, g[1:] * (1.0 - s1[1:] / s0[1:]) * h / (2.0 * h_last), torch.zeros_like(h))
+    rows = [sd * sd / r0, -s0 * sd / r0, s0 / r0, -sd / r0, g, g * down, g * up, cb]
+    return torch.stack(rows, dim=1).to(torch.float32).contiguous()
+
+
+def edm_step(xs: Tensor, f: Tensor, coef8: Tensor, rng4: Optional[Tensor] = None, scale: Optional[Tensor] = None,
+             clip: bool = False, order: int = 1, hist: Optional[Tensor] = None, out: Optional[Tensor] = None,
+             hist_out: Optional[Tensor] = None):
+    """One Karras (EDM) sampler update (adp_edm_step) on the scaled state xs [B, ...] and the net's output f, with coef8 =
+    device (a0, b0, e0, f0, c1, d1, s1, cb): c1 x0c + d1 nh [+ cb (x0c - hist)] [+ s1 z], x0 = a0 xs - b0 f, nh = e0 xs + f0 f,
+    z the normals of the rng4 row's stream, formed in registers (the values `randn` gives for the same row).  clip=False:
+    x0c = x0.  clip=True: x0 is clamped to the item's scale and divided by it (scale=None: clamped to [-1, 1]); nh comes from
+    the raw f.  order=1 returns xs_next and has no history; order=2 returns (xs_next, x0c) and needs `hist` (the previous
+    step's x0c), which a row with cb = 0 does not read.  A row with s1 = 0 does not read rng4, which may then be None (with
+    s1 != 0 a missing row gives NaN).  Every output may be its input."""
+    rows, per = _item_dims("edm_step", xs)
+    for name, other in (("f", f), ("hist", hist), ("out", out), ("hist_out", hist_out)):
+        if other is not None and other.shape != xs.shape:
+            raise ValueError(f"edm_step: {name} must have xs's shape {tuple(xs.shape)}; got {tuple(other.shape)}")
+    if coef8.dtype != torch.float32 or coef8.numel() != 8:
+        raise ValueError(f"edm_step: coef8 holds eight float32 values (a0, b0, e0, f0, c1, d1, s1, cb); got {coef8.dtype} "
+                         f"{tuple(coef8.shape)}")
+    if order not in (1, 2) or isinstance(order, bool):
+        raise ValueError(f"edm_step: order must be 1 or 2; got {order!r}")
+    _check_clip("edm_step", clip, scale, rows)
+    if order == 1:
+        if hist is not None or hist_out is not None:
+            raise ValueError("edm_step: the first-order step has no history")
+    elif hist is None:
+        raise ValueError("edm_step: the second-order step needs hist")
+    row = None if rng4 is None else _rng_row_ptr("edm_step", rng4)
+    if out is None:
+        out = torch.empty_like(xs)
+    if order == 2 and hist_out is None:
+        hist_out = torch.empty_like(xs)
+    _C.call("adp_edm_step", ptr(xs), ptr(f), ptr(hist), ptr(coef8), row, order, int(clip), ptr(scale), rows, per, ptr(out),
+            ptr(hist_out), _C.stream())
+    return out if order == 1 else (out, hist_out)
+
+
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
     """y2 [2B, ...] -> y2[B:] + (y2[:B] - y2[B:]) * scale."""
     half = y2.numel() // 2

@@ -11,7 +11,10 @@ first per repeat, one result line each (an A/B on one box: numbers of different 
 behind the quantile select for q > 0); `vsampler` is another name of `v`.  --train N times the replayed training step instead:
 RFDiffusion against VDiffusion on the same net shape, N steps each per repeat, interleaved.  --kernels N times the update
 kernels alone (adp_rf_step order 1 / 2 against adp_v_step / adp_v_step2, adp_rf_noise against adp_v_noise) from the library's
-own per-launch event pairs, N launches each, median."""
+own per-launch event pairs, N launches each, median.
+--sampler k [--order n] [--k-eta E] [--threshold q] runs it through KSampler (Karras / EDM: 1 step = 1 U-Net forward +
+adp_edm_step, behind the quantile select for q > 0) on KarrasSchedule(0.002, 80); --train and --kernels list KDiffusion and
+the adp_edm_* kernels next to the others."""
 import argparse
 import json
 import os
@@ -24,13 +27,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 
-SAMPLERS = ["v", "vsampler", "multistep", "threshold", "stochastic", "rf"]
+SAMPLERS = ["v", "vsampler", "multistep", "threshold", "stochastic", "rf", "k"]
 
 
 def train_bench(a, adp, dev):
-    """Replayed training steps (loss = model(x); loss.backward()) of RFDiffusion and VDiffusion, interleaved per repeat."""
+    """Replayed training steps (loss = model(x); loss.backward()) of RFDiffusion, KDiffusion and VDiffusion, interleaved per
+    repeat."""
     models = {}
-    for name, diffusion_t in (("RFDiffusion", adp.RFDiffusion), ("VDiffusion", adp.VDiffusion)):
+    for name, diffusion_t in (("RFDiffusion", adp.RFDiffusion), ("KDiffusion", adp.KDiffusion), ("VDiffusion", adp.VDiffusion)):
         torch.manual_seed(0)
         models[name] = adp.DiffusionModel(net_t=adp.UNetV0, in_channels=2, channels=bench.CHANNELS, factors=bench.FACTORS,
                                           items=bench.ITEMS, diffusion_t=diffusion_t).to(dev)
@@ -69,6 +73,8 @@ def kernel_bench(a, adp, dev):
     t = torch.rand(a.batch, generator=g).to(dev)
     row6 = ops.rf_table(torch.tensor([0.62, 0.55, 0.5]))[1].to(dev)
     ab4, ab6 = torch.rand(4, generator=g).to(dev), torch.rand(6, generator=g).to(dev)
+    k2, k_eta = ops.edm_table([80.0, 0.5, 0.002, 0.0])[1].to(dev), ops.edm_table([80.0, 0.5, 0.002, 0.0], order=1, eta=1.0)[1].to(dev)
+    rng, sigma = ops.rng_rows(0, [1])[0].to(dev), torch.rand(a.batch, generator=g).to(dev) + 0.1
     calls = {
         "adp_rf_step order 1": lambda: ops.rf_step(x, u, row6, out=out),
         "adp_v_step": lambda: ops.v_step(x, u, ab4, out=out),
@@ -77,6 +83,11 @@ def kernel_bench(a, adp, dev):
         "adp_rf_step order 1 static clamp": lambda: ops.rf_step(x, u, row6, clip=True, out=out),
         "adp_rf_noise": lambda: ops.rf_noise(x, u, t, x_t_out=o1, u_out=o2),
         "adp_v_noise": lambda: ops.v_noise(x, u, t),
+        "adp_edm_step order 1": lambda: ops.edm_step(x, u, k2, out=out),
+        "adp_edm_step order 2": lambda: ops.edm_step(x, u, k2, order=2, hist=h1, out=out, hist_out=o1),
+        "adp_edm_step order 1 eta 1": lambda: ops.edm_step(x, u, k_eta, rng, out=out),
+        "adp_v_step_eta": lambda: ops.v_step_eta(x, u, ab6[:5], rng, out=out),
+        "adp_edm_noise": lambda: ops.edm_noise(x, u, sigma, 0.5, x_in_out=o1, target_out=o2),
     }
     for fn in calls.values():
         fn()
@@ -103,9 +114,11 @@ def main():
     ap.add_argument("--threshold", type=float, default=None,
                     help="--sampler threshold / stochastic: dynamic_threshold (0 = static clamp; threshold's default 0.995)")
     ap.add_argument("--eta", type=float, default=1.0, help="--sampler stochastic: eta in [0, 1]")
+    ap.add_argument("--k-eta", type=float, default=0.0, help="--sampler k: eta in [0, 1] (eta > 0 needs --order 1)")
     ap.add_argument("--order", type=int, default=None,
-                    help="--sampler multistep / threshold / rf: order (their default if unset)")
-    ap.add_argument("--train", type=int, default=0, help="time N replayed training steps of RFDiffusion and VDiffusion instead")
+                    help="--sampler multistep / threshold / rf / k: order (their default if unset)")
+    ap.add_argument("--train", type=int, default=0,
+                    help="time N replayed training steps of RFDiffusion, KDiffusion and VDiffusion instead")
     ap.add_argument("--kernels", type=int, default=0, help="time N launches of each update kernel alone instead")
     ap.add_argument("--repeats", type=int, default=1)
     a = ap.parse_args()
@@ -120,7 +133,7 @@ def main():
     samplers, kwargs, run_kw = [], [], []
     for name in names:
         sampler_t = {"v": adp.VSampler, "vsampler": adp.VSampler, "multistep": adp.VMultistepSampler,
-                     "threshold": adp.VThresholdSampler, "stochastic": adp.VStochasticSampler, "rf": adp.RFSampler}[name]
+                     "threshold": adp.VThresholdSampler, "stochastic": adp.VStochasticSampler, "rf": adp.RFSampler, "k": adp.KSampler}[name]
         kw = {}
         if name == "threshold":
             kw["dynamic_threshold"] = 0.995 if a.threshold is None else a.threshold
@@ -128,13 +141,15 @@ def main():
             kw["eta"] = a.eta
             if a.threshold is not None:
                 kw["dynamic_threshold"] = a.threshold
-        if name == "rf" and a.threshold is not None:
+        if name in ("rf", "k") and a.threshold is not None:
             kw["dynamic_threshold"] = a.threshold
-        if a.order is not None and name in ("multistep", "threshold", "rf"):
+        if name == "k":
+            kw.update(schedule=adp.KarrasSchedule(0.002, 80.0), eta=a.k_eta)
+        if a.order is not None and name in ("multistep", "threshold", "rf", "k"):
             kw["order"] = a.order
         samplers.append(sampler_t(net=net, use_graph=bool(a.graph), **kw))
         kwargs.append(kw)
-        run_kw.append({"seed": 0} if name == "stochastic" else {})
+        run_kw.append({"seed": 0} if name in ("stochastic", "k") else {})
     with torch.no_grad():
         for s, rk in zip(samplers, run_kw):
             s(noise, num_steps=2, **rk)  # warm-up + graph capture
@@ -154,7 +169,7 @@ def main():
                "ms_per_step": round(dt / a.steps * 1e3, 3), "batch": a.batch, "num_steps": a.steps,
                "launch": "hipGraph replay" if a.graph else "eager", "finite": bool(torch.isfinite(out).all())}
         if name not in ("v", "vsampler"):
-            res["sampler_kwargs"] = kw
+            res["sampler_kwargs"] = {k: v for k, v in kw.items() if k != "schedule"}
         if a.repeats > 1:
             res["ms_per_step_runs"] = [round(t / a.steps * 1e3, 3) for t in ts]
         print(json.dumps(res))
