@@ -205,11 +205,18 @@ ABI["adp_edm.h"] = {
     "adp_edm_step": (c_int, [P, P, P, P, P, I, I, P, I, I, P, P, P]),
 }
 
+# RePaint inpainting: one resample (the objective's first-order update, the jump back, the known region) per objective
+ABI["adp_repaint.h"] = {
+    "adp_repaint_v_step": (c_int, [P, P, P, P, P, P, I, P, I, I, P, P]),
+    "adp_repaint_rf_step": (c_int, [P, P, P, P, P, P, I, P, I, I, P, P]),
+    "adp_repaint_k_step": (c_int, [P, P, P, P, P, P, I, P, I, I, P, P]),
+}
+
 
 # extension header -> the csrc/ file that includes and implements it (adp.h is implemented by all of them)
 HEADER_SOURCE = {"adp_ar.h": "elementwise.hip", "adp_lt.h": "lt.hip", "adp_enc.h": "encoder.hip", "adp_t5.h": "t5.hip",
                  "adp_rng.h": "rng.hip", "adp_clip.h": "clip.hip", "adp_gated.h": "gated.hip", "adp_sde.h": "sde.hip",
-                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip"}
+                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip", "adp_repaint.h": "repaint.hip"}
 
 # the whole C-ABI, name -> (restype, argtypes): what `_bind` binds and `call` / `call_value` / `query` resolve
 SIGNATURES = {}

@@ -19,6 +19,7 @@ from .edm import KarrasSchedule, KDiffusion, KSampler, LogNormalDistribution
 from .losses import MultiResolutionSTFTLoss, STFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
 from .optim import AdamW
+from .repaint import KRepainter, RFRepainter, VRepainter
 from .rf import LogitNormalDistribution, RFDiffusion, RFSampler
 from .unet import UNetV0Net
 
@@ -56,4 +57,5 @@ __all__ = [
     "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
     "RFDiffusion", "RFSampler", "LogitNormalDistribution",
     "KDiffusion", "KSampler", "KarrasSchedule", "LogNormalDistribution",
+    "VRepainter", "RFRepainter", "KRepainter",
 ]

@@ -86,31 +86,7 @@ __global__ __launch_bounds__(256) void edm_noise_kernel(const float* x, const fl
   }
 }
 
-// ---- the sampler update
-struct EdmCoef {
-  float a0, b0, e0, f0, c1, d1, s1, cb;
-};
-
-struct EdmStepped {
-  float xn, x0c;
-};
-
-// One element, by the rounding sequence of the header.  x0 and its clamps are sampler_update.h's clip_x0 and clipped, the
-// ones clip.hip's select ranks and adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale
-// stays NaN.
-template <int CLIP, int ORDER>
-__device__ __forceinline__ EdmStepped edm_step_elem(const EdmCoef& c, float s, float xv, float fv, float hv, float z,
-                                                    bool multi, bool noisy) {
-  const float x0 = clip_x0(c.a0, xv, c.b0, fv);
-  const float nh = fma_rn(c.e0, xv, c.f0 * fv);
-  EdmStepped r;
-  r.x0c = clipped<CLIP>(x0, s);
-  r.xn = fma_rn(c.c1, r.x0c, c.d1 * nh);
-  if (ORDER == 2 && multi) r.xn = fma_rn(c.cb, r.x0c - hv, r.xn);
-  if (noisy) r.xn = fma_rn(c.s1, z, r.xn);
-  return r;
-}
-
+// ---- the sampler update: edm_step_elem of sampler_update.h behind x0 = clip_x0(...)
 // VEC: xs, f, xo (and hist, ho for ORDER 2) are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per].
 template <int CLIP, int ORDER, bool VEC>
 __global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const float* f, const float* hist,
@@ -143,7 +119,8 @@ __global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const flo
       f32x4 o, w;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], xv[k], fv[k], hv[k], z[k], multi, noisy);
+        const float x0 = clip_x0(c.a0, xv[k], c.b0, fv[k]);
+        const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], x0, xv[k], fv[k], hv[k], z[k], multi, noisy);
         o[k] = r.xn;
         w[k] = r.x0c;
       }
@@ -154,7 +131,9 @@ __global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const flo
       for (int k = 0; k < 4; ++k)
         if (e + k < n) {
           const float hv = multi ? hist[e + k] : 0.0f;
-          const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], x[e + k], f[e + k], hv, z[k], multi, noisy);
+          const float xv = x[e + k], fv = f[e + k];
+          const float x0 = clip_x0(c.a0, xv, c.b0, fv);
+          const EdmStepped r = edm_step_elem<CLIP, ORDER>(c, s[k], x0, xv, fv, hv, z[k], multi, noisy);
           xo[e + k] = r.xn;
           if (ORDER == 2) ho[e + k] = r.x0c;
         }

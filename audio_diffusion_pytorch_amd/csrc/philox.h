@@ -1,6 +1,7 @@
 // The counter-based normal generator of include/adp_rng.h as device functions: Philox4x32-10 on a (seed, draw) row and
 // Box-Muller on its words.  Private to the kernel sources that form a row's stream in registers (rng.hip: adp_randn and
-// the VInpainter step; sde.hip: the stochastic sampler step), so that all of them give the same bits for the same row.
+// the VInpainter step; sde.hip, edm.hip: the stochastic sampler steps; repaint.hip: the RePaint resample), so that all of them
+// give the same bits for the same row.
 #pragma once
 #include "adp_rt.h"
 

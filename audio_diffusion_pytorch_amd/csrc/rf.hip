@@ -59,33 +59,7 @@ __global__ __launch_bounds__(256) void rf_noise_kernel(const float* x, const flo
   }
 }
 
-// ---- the sampler update
-struct RfCoef {
-  float a0, b0, c0, a1, c1, cb;
-};
-
-struct RfStepped {
-  float xn, w;
-};
-
-// One element, by the rounding sequence of the header.  x0 and its clamps are sampler_update.h's clip_x0 and clipped, the
-// ones clip.hip's select ranks and adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale
-// stays NaN.
-template <int CLIP, int ORDER>
-__device__ __forceinline__ RfStepped rf_step_elem(const RfCoef& c, float s, float xv, float uv, float hv, bool multi) {
-  const float x0 = clip_x0(c.a0, xv, c.b0, uv);
-  const float eps = fma_rn(c.c0, uv, xv);
-  const float x0c = clipped<CLIP>(x0, s);
-  RfStepped r;
-  r.xn = fma_rn(c.c1, x0c, c.a1 * eps);
-  r.w = 0.0f;
-  if (ORDER == 2) {
-    r.w = eps - x0c;
-    if (multi) r.xn = fma_rn(c.cb, r.w - hv, r.xn);
-  }
-  return r;
-}
-
+// ---- the sampler update: rf_step_elem of sampler_update.h behind x0 = clip_x0(...)
 // VEC: x, u, xo (and hist, ho for ORDER 2) are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per].
 template <int CLIP, int ORDER, bool VEC>
 __global__ __launch_bounds__(256) void rf_step_kernel(const float* x, const float* u, const float* hist, const float* coef6,
@@ -104,7 +78,8 @@ __global__ __launch_bounds__(256) void rf_step_kernel(const float* x, const floa
       f32x4 o, w;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const RfStepped r = rf_step_elem<CLIP, ORDER>(c, s[k], xv[k], uv[k], hv[k], multi);
+        const float x0 = clip_x0(c.a0, xv[k], c.b0, uv[k]);
+        const RfStepped r = rf_step_elem<CLIP, ORDER>(c, s[k], x0, xv[k], uv[k], hv[k], multi);
         o[k] = r.xn;
         w[k] = r.w;
       }
@@ -115,7 +90,8 @@ __global__ __launch_bounds__(256) void rf_step_kernel(const float* x, const floa
       for (int k = 0; k < 4; ++k)
         if (e + k < n) {
           const float hv = multi ? hist[e + k] : 0.0f;
-          const RfStepped r = rf_step_elem<CLIP, ORDER>(c, s[k], x[e + k], u[e + k], hv, multi);
+          const float xv = x[e + k], uv = u[e + k];
+          const RfStepped r = rf_step_elem<CLIP, ORDER>(c, s[k], clip_x0(c.a0, xv, c.b0, uv), xv, uv, hv, multi);
           xo[e + k] = r.xn;
           if (ORDER == 2) ho[e + k] = r.w;
         }

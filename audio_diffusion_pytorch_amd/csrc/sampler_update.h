@@ -1,4 +1,4 @@
-// What the sampler-update kernels share (clip.hip, sde.hip, rf.hip, rng.hip), each decision stated once: the arithmetic of
+// What the sampler-update kernels share (clip.hip, sde.hip, rf.hip, edm.hip, repaint.hip, rng.hip), each decision stated once: the arithmetic of
 // the predicted clean value and its clamps, whose bits include/adp_clip.h, adp_sde.h and adp_rf.h promise to be the ones
 // adp_clip_scale ranked; the group-of-four geometry of the flat elementwise kernels; the host checks and the choice of a
 // kernel instantiation.  Private to those sources.
@@ -38,6 +38,72 @@ enum { CLIP_NONE = 0, CLIP_STATIC = 1, CLIP_SCALE = 2 };
 template <int CLIP>
 __device__ __forceinline__ float clipped(float x0, float s) {
   return CLIP == CLIP_STATIC ? clamp1(x0) : CLIP == CLIP_SCALE ? clamp_div(x0, s) : x0;
+}
+
+// ---- the element updates of the three objectives, each stated once: sde.hip, rf.hip and edm.hip wrap them in their step
+// kernels, repaint.hip puts the RePaint jump and the known region behind them.  Every caller forms x0 itself, by
+// clip_x0(c.a0, x, c.b0, p) and nothing else, and hands it in: the one spelling a reader (and tests/test_clip_placement.py)
+// finds in every source that clamps x0.
+// v-objective (include/adp_sde.h): a1 clip(a0 x - b0 v) + ce (b0 x + a0 v) [+ cz z]
+struct SdeCoef {
+  float a0, b0, a1, ce, cz;
+};
+
+// One element behind x0 = clip_x0(c.a0, xv, c.b0, vv).  x0 and its clamps are clip_x0 and clipped above, the ones clip.hip's
+// select ranks and adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale stays NaN.
+template <int CLIP>
+__device__ __forceinline__ float sde_elem(const SdeCoef& c, float s, float x0, float xv, float vv, float z, bool noisy) {
+  const float eps = fma_rn(c.b0, xv, c.a0 * vv);
+  const float x0c = clipped<CLIP>(x0, s);
+  const float xn = fma_rn(c.a1, x0c, c.ce * eps);
+  return noisy ? fma_rn(c.cz, z, xn) : xn;
+}
+
+// rectified flow (include/adp_rf.h): c1 clip(a0 x - b0 u) + a1 (c0 u + x) [+ cb (w - hist)]
+struct RfCoef {
+  float a0, b0, c0, a1, c1, cb;
+};
+
+struct RfStepped {
+  float xn, w;
+};
+
+// One element behind x0 = clip_x0(c.a0, xv, c.b0, uv), by the rounding sequence of the header.
+template <int CLIP, int ORDER>
+__device__ __forceinline__ RfStepped rf_step_elem(const RfCoef& c, float s, float x0, float xv, float uv, float hv,
+                                                  bool multi) {
+  const float eps = fma_rn(c.c0, uv, xv);
+  const float x0c = clipped<CLIP>(x0, s);
+  RfStepped r;
+  r.xn = fma_rn(c.c1, x0c, c.a1 * eps);
+  r.w = 0.0f;
+  if (ORDER == 2) {
+    r.w = eps - x0c;
+    if (multi) r.xn = fma_rn(c.cb, r.w - hv, r.xn);
+  }
+  return r;
+}
+
+// Karras / EDM (include/adp_edm.h): c1 clip(a0 xs - b0 F) + d1 (e0 xs + f0 F) [+ cb (x0c - hist)] [+ s1 z]
+struct EdmCoef {
+  float a0, b0, e0, f0, c1, d1, s1, cb;
+};
+
+struct EdmStepped {
+  float xn, x0c;
+};
+
+// One element behind x0 = clip_x0(c.a0, xv, c.b0, fv), by the rounding sequence of the header.
+template <int CLIP, int ORDER>
+__device__ __forceinline__ EdmStepped edm_step_elem(const EdmCoef& c, float s, float x0, float xv, float fv, float hv,
+                                                    float z, bool multi, bool noisy) {
+  const float nh = fma_rn(c.e0, xv, c.f0 * fv);
+  EdmStepped r;
+  r.x0c = clipped<CLIP>(x0, s);
+  r.xn = fma_rn(c.c1, r.x0c, c.d1 * nh);
+  if (ORDER == 2 && multi) r.xn = fma_rn(c.cb, r.x0c - hv, r.xn);
+  if (noisy) r.xn = fma_rn(c.s1, z, r.xn);
+  return r;
 }
 
 // ---- groups of four: one thread owns one group of four consecutive elements per pass, in a grid-stride loop.

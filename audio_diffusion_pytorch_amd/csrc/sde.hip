@@ -16,21 +16,6 @@ namespace {
 using namespace philox;
 using namespace upd;
 
-struct SdeCoef {
-  float a0, b0, a1, ce, cz;
-};
-
-// One element.  x0 and its clamps are sampler_update.h's clip_x0 and clipped, the ones clip.hip's select ranks and
-// adp_clip_step applies: the scale was selected from those bits, and a NaN x0 or scale stays NaN.
-template <int CLIP>
-__device__ __forceinline__ float sde_elem(const SdeCoef& c, float s, float xv, float vv, float z, bool noisy) {
-  const float x0 = clip_x0(c.a0, xv, c.b0, vv);
-  const float eps = fma_rn(c.b0, xv, c.a0 * vv);
-  const float x0c = clipped<CLIP>(x0, s);
-  const float xn = fma_rn(c.a1, x0c, c.ce * eps);
-  return noisy ? fma_rn(c.cz, z, xn) : xn;
-}
-
 // VEC: x, v and xo are 16-byte aligned.  CLIP_SCALE: element i takes scale[i / per]; a group may straddle items
 // (item_values4).
 template <int CLIP, bool VEC>
@@ -60,12 +45,16 @@ __global__ __launch_bounds__(256) void v_step_eta_kernel(const float* x, const f
       const f32x4 xv = *(const f32x4*)(x + e), vv = *(const f32x4*)(v + e);
       f32x4 o;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = sde_elem<CLIP>(c, s[k], xv[k], vv[k], z[k], noisy);
+      for (int k = 0; k < 4; ++k)
+        o[k] = sde_elem<CLIP>(c, s[k], clip_x0(c.a0, xv[k], c.b0, vv[k]), xv[k], vv[k], z[k], noisy);
       *(f32x4*)(xo + e) = o;
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (e + k < n) xo[e + k] = sde_elem<CLIP>(c, s[k], x[e + k], v[e + k], z[k], noisy);
+        if (e + k < n) {
+          const float xv = x[e + k], vv = v[e + k];
+          xo[e + k] = sde_elem<CLIP>(c, s[k], clip_x0(c.a0, xv, c.b0, vv), xv, vv, z[k], noisy);
+        }
     }
   }
 }

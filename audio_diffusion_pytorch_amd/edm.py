@@ -164,7 +164,7 @@ class KSampler(_Thresholded, VSampler):
     `forward(x_noisy, num_steps, start=clip)`: x_noisy is UNIT noise; the run starts from start + sigma_0 x_noisy (start
     omitted: zero), formed by adp_edm_noise, whose first output is already the scaled state.
 
-    Out of scope: an inpainter, `ar.ARVSampler`, a second-order stochastic update, Heun / two-evaluation steps."""
+    The inpainter on this state is `repaint.KRepainter`.  Out of scope: `ar.ARVSampler`, a second-order stochastic update, Heun / two-evaluation steps."""
 
     diffusion_types = [KDiffusion]
 

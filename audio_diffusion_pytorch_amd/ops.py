@@ -1084,6 +1084,103 @@ def edm_step(xs: Tensor, f: Tensor, coef8: Tensor, rng4: Optional[Tensor] = None
     return out if order == 1 else (out, hist_out)
 
 
+# ---- include/adp_repaint.h: RePaint inpainting (the objective's first-order update, the jump back, the known region)
+
+REPAINT_OBJECTIVES = {"v": ("adp_repaint_v_step", 4), "rf": ("adp_repaint_rf_step", 6), "k": ("adp_repaint_k_step", 8)}
+
+
+def _repaint_objective(what: str, objective):
+    if objective not in REPAINT_OBJECTIVES:
+        raise ValueError(f"{what}: objective must be one of {tuple(REPAINT_OBJECTIVES)}; got {objective!r}")
+    return REPAINT_OBJECTIVES[objective]
+
+
+def repaint_table(objective: str, levels, num_resamples: int, sigma_data: float = 0.5) -> Tensor:
+    """The coefficient rows [N * R, W + 4] of a RePaint run over the levels l_0 .. l_N with R = num_resamples
+    (include/adp_repaint.h), float32 on the CPU, in loop order (step i, resample r at row i R + r): the objective's own
+    first-order step row for (i, i + 1) -- `VSampler`'s (a_i, b_i, a_{i+1}, b_{i+1}) formed in float32 where `levels` lives
+    (W = 4), `rf_table(order=1)`'s (W = 6), `edm_table(order=1, eta=0)`'s (W = 8) -- then (A, S, P, Q), formed in float64 and
+    rounded once.  With x_l = a_l x0 + b_l n, (a, b) = (cos, sin)(l pi / 2) | (1 - l, l) | (1, l) for "v" | "rf" | "k":
+
+        r < R - 1 (jump back to level i):  A = a_i / a_{i+1}   S = sqrt(max(b_i^2 - (A b_{i+1})^2, 0))   P = a_i       Q = b_i
+        r = R - 1 (move on to level i+1):  A = 1               S = 0                                     P = a_{i+1}   Q = b_{i+1}
+
+    For "k" the state is scaled by c_in(l) = 1 / sqrt(l^2 + sigma_data^2) and the factors fold in: A = c_in(l_i) / g with g the
+    factor the step row applied, S = c_in(l_i) sqrt(l_i^2 - l_{i+1}^2), P = c_in(l_j), Q = c_in(l_j) l_j; the last row of the
+    run has P = 1, Q = 0 (the run ends unscaled, on the source itself).  The levels must fall strictly; the last may be 0."""
+    _, words = _repaint_objective("repaint_table", objective)
+    if isinstance(num_resamples, bool) or not isinstance(num_resamples, int) or num_resamples < 1:
+        raise ValueError(f"repaint_table: num_resamples must be an integer >= 1; got {num_resamples!r}")
+    lv = torch.as_tensor(levels).detach()
+    l = lv.to(device="cpu", dtype=torch.float64).reshape(-1)
+    if l.numel() < 1:
+        raise ValueError("repaint_table: levels must hold at least l_0")
+    n, R = l.numel() - 1, num_resamples
+    if not bool(torch.isfinite(l).all()):
+        raise ValueError("repaint_table: every level of the schedule must be finite")
+    if bool((l[1:] >= l[:-1]).any()):
+        raise ValueError("repaint_table: the levels of the schedule must fall strictly; "
+                         f"level {int((l[1:] >= l[:-1]).nonzero()[0]) + 1} does not")
+    if l[-1] < 0 or (objective != "k" and l[0] > 1):
+        raise ValueError(f"repaint_table: the levels of the schedule must lie in [0, {'inf)' if objective == 'k' else '1]'}; "
+                         f"got {l[0].item()} .. {l[-1].item()}")
+    if objective == "v":
+        s32 = lv.to(torch.float32).reshape(-1)
+        angle = s32 * torch.pi / 2        # (diffusion.alpha_beta's float32 arithmetic, where the levels live)
+        al, be = torch.cos(angle), torch.sin(angle)
+        step = torch.stack([al[:-1], be[:-1], al[1:], be[1:]], dim=1).to("cpu")
+        a, b = torch.cos(l * (torch.pi / 2)), torch.sin(l * (torch.pi / 2))
+    elif objective == "rf":
+        step = rf_table(l, order=1)
+        a, b = 1.0 - l, l
+    else:
+        sd = _check_sigma_data("repaint_table", sigma_data)
+        step = edm_table(l, sd, order=1, eta=0.0)
+        a, b = torch.ones_like(l), l
+    A = a[:-1] / a[1:]
+    S = torch.sqrt((b[:-1] * b[:-1] - (A * b[1:]) ** 2).clamp_min(0.0))
+    jump = torch.stack([A, S, a[:-1], b[:-1]], dim=1)
+    move = torch.stack([torch.ones(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64), a[1:], b[1:]], dim=1)
+    if objective == "k":
+        c_in = 1.0 / torch.sqrt(l * l + sd * sd)
+        g = c_in[1:].clone()
+        if n > 0:
+            g[-1] = 1.0
+        jump = torch.stack([c_in[:-1] / g, c_in[:-1] * S, c_in[:-1], c_in[:-1] * b[:-1]], dim=1)
+        move[:, 2], move[:, 3] = c_in[1:], c_in[1:] * b[1:]
+        if n > 0:
+            move[-1, 2], move[-1, 3] = 1.0, 0.0
+    blend = jump[:, None, :].repeat(1, R, 1)
+    blend[:, R - 1] = move
+    rows = torch.cat([step[:, None, :].expand(n, R, words), blend.to(torch.float32)], dim=2)
+    return rows.reshape(n * R, words + 4).contiguous()
+
+
+def repaint_step(objective: str, x: Tensor, p: Tensor, source: Tensor, mask_u8: Tensor, row: Tensor,
+                 rng4: Optional[Tensor] = None, scale: Optional[Tensor] = None, clip: bool = False,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """One RePaint resample (adp_repaint_{v,rf,k}_step) on x [B, ...] and the net's output p: the objective's first-order
+    update by the first W values of `row` (one row of `repaint_table`, W + 4 float32 values on the device), then with its last
+    four (A, S, P, Q): y = A y + S z, and P source + Q z where mask_u8 is set; z the normals of the rng4 row's stream,
+    formed in registers (the values `randn` gives for the same row).  clip, scale: as in `rf_step`.  A row with S = Q = 0
+    does not read rng4, which may then be None (where a normal is needed a missing row gives NaN).  `out` may be x."""
+    entry, words = _repaint_objective("repaint_step", objective)
+    rows, per = _item_dims("repaint_step", x)
+    for name, other in (("p", p), ("source", source), ("mask", mask_u8), ("out", out)):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"repaint_step: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    if row.dtype != torch.float32 or row.numel() != words + 4:
+        raise ValueError(f"repaint_step: row holds {words + 4} float32 values for objective {objective!r} (the step's "
+                         f"{words}, then A, S, P, Q); got {row.dtype} {tuple(row.shape)}")
+    _check_clip("repaint_step", clip, scale, rows)
+    rng = None if rng4 is None else _rng_row_ptr("repaint_step", rng4)
+    if out is None:
+        out = torch.empty_like(x)
+    _C.call(entry, ptr(x), ptr(p), ptr(source), ptr(mask_u8, torch.uint8), ptr(row), rng, int(clip), ptr(scale), rows, per,
+            ptr(out), _C.stream())
+    return out
+
+
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
     """y2 [2B, ...] -> y2[B:] + (y2[:B] - y2[B:]) * scale."""
     half = y2.numel() // 2

@@ -14,7 +14,12 @@ kernels alone (adp_rf_step order 1 / 2 against adp_v_step / adp_v_step2, adp_rf_
 own per-launch event pairs, N launches each, median.
 --sampler k [--order n] [--k-eta E] [--threshold q] runs it through KSampler (Karras / EDM: 1 step = 1 U-Net forward +
 adp_edm_step, behind the quantile select for q > 0) on KarrasSchedule(0.002, 80); --train and --kernels list KDiffusion and
-the adp_edm_* kernels next to the others."""
+the adp_edm_* kernels next to the others.
+--sampler repaint-v | repaint-rf | repaint-k [--resamples R] [--threshold q] runs the RePaint inpainters (VRepainter,
+RFRepainter, KRepainter: 1 resample = 1 U-Net forward + adp_repaint_*_step, behind the quantile select for q > 0) on a
+continuation mask (the first half known), --steps steps of R resamples each, and reports ms per resample; `inpaint` is
+VInpainter(noise="philox", use_graph=True) on the same problem, for an A/B through --also.  --kernels lists the
+adp_repaint_*_step kernels next to adp_v_inpaint_step_rng."""
 import argparse
 import json
 import os
@@ -27,7 +32,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 
-SAMPLERS = ["v", "vsampler", "multistep", "threshold", "stochastic", "rf", "k"]
+INPAINTERS = ["repaint-v", "repaint-rf", "repaint-k", "inpaint"]
+SAMPLERS = ["v", "vsampler", "multistep", "threshold", "stochastic", "rf", "k"] + INPAINTERS
 
 
 def train_bench(a, adp, dev):
@@ -75,6 +81,8 @@ def kernel_bench(a, adp, dev):
     ab4, ab6 = torch.rand(4, generator=g).to(dev), torch.rand(6, generator=g).to(dev)
     k2, k_eta = ops.edm_table([80.0, 0.5, 0.002, 0.0])[1].to(dev), ops.edm_table([80.0, 0.5, 0.002, 0.0], order=1, eta=1.0)[1].to(dev)
     rng, sigma = ops.rng_rows(0, [1])[0].to(dev), torch.rand(a.batch, generator=g).to(dev) + 0.1
+    half = torch.zeros(a.batch, 2, bench.LENGTH, dtype=torch.uint8, device=dev)
+    half[..., :bench.LENGTH // 2] = 1   # (continuation: the first half keeps the source)
     calls = {
         "adp_rf_step order 1": lambda: ops.rf_step(x, u, row6, out=out),
         "adp_v_step": lambda: ops.v_step(x, u, ab4, out=out),
@@ -88,7 +96,14 @@ def kernel_bench(a, adp, dev):
         "adp_edm_step order 1 eta 1": lambda: ops.edm_step(x, u, k_eta, rng, out=out),
         "adp_v_step_eta": lambda: ops.v_step_eta(x, u, ab6[:5], rng, out=out),
         "adp_edm_noise": lambda: ops.edm_noise(x, u, sigma, 0.5, x_in_out=o1, target_out=o2),
+        "adp_v_inpaint_step_rng": lambda: ops.v_inpaint_step_rng(x, u, h1, half, ab4, rng, out=out),
     }
+    for obj, levels in (("v", [0.62, 0.55, 0.5]), ("rf", [0.62, 0.55, 0.5]), ("k", [80.0, 0.5, 0.002])):
+        table = ops.repaint_table(obj, torch.tensor(levels), 2).to(dev)
+        for kind, row in (("jump", table[0]), ("move on", table[1])):
+            calls[f"adp_repaint_{obj}_step {kind}"] = lambda obj=obj, row=row: ops.repaint_step(obj, x, u, h1, half, row, rng, out=out)
+    static_row = ops.repaint_table("v", torch.tensor([0.62, 0.55]), 2)[0].to(dev)
+    calls["adp_repaint_v_step jump static clamp"] = lambda: ops.repaint_step("v", x, u, h1, half, static_row, rng, clip=True, out=out)
     for fn in calls.values():
         fn()
     torch.cuda.synchronize()
@@ -117,6 +132,7 @@ def main():
     ap.add_argument("--k-eta", type=float, default=0.0, help="--sampler k: eta in [0, 1] (eta > 0 needs --order 1)")
     ap.add_argument("--order", type=int, default=None,
                     help="--sampler multistep / threshold / rf / k: order (their default if unset)")
+    ap.add_argument("--resamples", type=int, default=4, help="--sampler repaint-* / inpaint: num_resamples")
     ap.add_argument("--train", type=int, default=0,
                     help="time N replayed training steps of RFDiffusion, KDiffusion and VDiffusion instead")
     ap.add_argument("--kernels", type=int, default=0, help="time N launches of each update kernel alone instead")
@@ -132,6 +148,18 @@ def main():
     names = [a.sampler] + list(a.also)
     samplers, kwargs, run_kw = [], [], []
     for name in names:
+        if name in INPAINTERS:
+            kw = {} if a.threshold is None or name == "inpaint" else {"dynamic_threshold": a.threshold}
+            if name == "inpaint":
+                samplers.append(adp.VInpainter(net=net, noise="philox", use_graph=bool(a.graph)))
+            elif name == "repaint-k":
+                samplers.append(adp.KRepainter(net=net, schedule=adp.KarrasSchedule(0.002, 80.0), use_graph=bool(a.graph), **kw))
+            else:
+                cls = adp.VRepainter if name == "repaint-v" else adp.RFRepainter
+                samplers.append(cls(net=net, use_graph=bool(a.graph), **kw))
+            kwargs.append(kw)
+            run_kw.append({"seed": 0})
+            continue
         sampler_t = {"v": adp.VSampler, "vsampler": adp.VSampler, "multistep": adp.VMultistepSampler,
                      "threshold": adp.VThresholdSampler, "stochastic": adp.VStochasticSampler, "rf": adp.RFSampler, "k": adp.KSampler}[name]
         kw = {}
@@ -150,20 +178,38 @@ def main():
         samplers.append(sampler_t(net=net, use_graph=bool(a.graph), **kw))
         kwargs.append(kw)
         run_kw.append({"seed": 0} if name in ("stochastic", "k") else {})
+    known = torch.zeros(a.batch, 2, bench.LENGTH, dtype=torch.bool, device=dev)
+    known[..., :bench.LENGTH // 2] = True   # (continuation of a clip: the first half keeps the source)
+
+    def run(name, s, steps, rk):
+        if name in INPAINTERS:
+            return s(noise, known, num_steps=steps, num_resamples=a.resamples, **rk)
+        return s(noise, num_steps=steps, **rk)
+
     with torch.no_grad():
-        for s, rk in zip(samplers, run_kw):
-            s(noise, num_steps=2, **rk)  # warm-up + graph capture
+        for name, s, rk in zip(names, samplers, run_kw):
+            run(name, s, 2, rk)  # warm-up + graph capture
         times = [[] for _ in samplers]
         outs = [None] * len(samplers)
         for _ in range(max(1, a.repeats)):
-            for k, (s, rk) in enumerate(zip(samplers, run_kw)):
+            for k, (name, s, rk) in enumerate(zip(names, samplers, run_kw)):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                outs[k] = s(noise, num_steps=a.steps, **rk)
+                outs[k] = run(name, s, a.steps, rk)
                 torch.cuda.synchronize()
                 times[k].append(time.perf_counter() - t0)
     for name, s, kw, ts, out in zip(names, samplers, kwargs, times, outs):
         dt = sorted(ts)[len(ts) // 2]
+        if name in INPAINTERS:
+            n = a.steps * a.resamples
+            res = {"metric": f"inpainter resamples/s ({type(s).__name__}, UNetV0 forward only)", "value": round(n / dt, 2),
+                   "ms_per_resample": round(dt / n * 1e3, 3), "batch": a.batch, "num_steps": a.steps,
+                   "num_resamples": a.resamples, "launch": "hipGraph replay" if a.graph else "eager",
+                   "finite": bool(torch.isfinite(out).all()), "inpainter_kwargs": kw}
+            if a.repeats > 1:
+                res["ms_per_resample_runs"] = [round(t / n * 1e3, 3) for t in ts]
+            print(json.dumps(res))
+            continue
         res = {"metric": f"sampler steps/s ({type(s).__name__}, UNetV0 forward only)",
                "value": round(a.steps / dt, 2),
                "ms_per_step": round(dt / a.steps * 1e3, 3), "batch": a.batch, "num_steps": a.steps,
