@@ -212,11 +212,19 @@ ABI["adp_repaint.h"] = {
     "adp_repaint_k_step": (c_int, [P, P, P, P, P, P, I, P, I, I, P, P]),
 }
 
+# grouped (stereo sum / difference) and mel-scaled multi-resolution STFT loss, and its FIR pre-filter
+ABI["adp_spec.h"] = {
+    "adp_spec_loss_ws_bytes": (I, [I, I, I, I, P, P, I]),
+    "adp_spec_loss_fwd": (c_int, [P, P, I, I, I, I, P, P, P, P, F, F, F, F, F, F, P, P, P]),
+    "adp_spec_loss_bwd": (c_int, [P, P, P, P, I, I, I, I, P, P, P, P, P, F, F, F, F, F, F, P, P, P]),
+    "adp_spec_fir": (c_int, [P, P, I, I, I, P, P]),
+}
+
 
 # extension header -> the csrc/ file that includes and implements it (adp.h is implemented by all of them)
 HEADER_SOURCE = {"adp_ar.h": "elementwise.hip", "adp_lt.h": "lt.hip", "adp_enc.h": "encoder.hip", "adp_t5.h": "t5.hip",
                  "adp_rng.h": "rng.hip", "adp_clip.h": "clip.hip", "adp_gated.h": "gated.hip", "adp_sde.h": "sde.hip",
-                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip", "adp_repaint.h": "repaint.hip"}
+                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip", "adp_repaint.h": "repaint.hip", "adp_spec.h": "spectral.hip"}
 
 # the whole C-ABI, name -> (restype, argtypes): what `_bind` binds and `call` / `call_value` / `query` resolve
 SIGNATURES = {}

@@ -17,6 +17,7 @@ from .diffusion import (
 )
 from .edm import KarrasSchedule, KDiffusion, KSampler, LogNormalDistribution
 from .losses import MultiResolutionSTFTLoss, STFTLoss
+from .spectral import MelSTFTLoss, SumAndDifferenceSTFTLoss
 from .models import AdapterBase, DiffusionAE, DiffusionModel, DiffusionUpsampler, EncoderBase
 from .optim import AdamW
 from .repaint import KRepainter, RFRepainter, VRepainter
@@ -54,7 +55,7 @@ __all__ = [
     "AppendChannelsPlugin", "UNetV0", "XUNet", "UNetV0Net", "Diffusion", "Distribution", "LinearSchedule", "Sampler",
     "Schedule", "UniformDistribution", "VDiffusion", "VInpainter", "VSampler", "VMultistepSampler", "VThresholdSampler", "VStochasticSampler", "DiffusionModel",
     "DiffusionUpsampler", "DiffusionAE", "EncoderBase", "AdapterBase", "ClassifierFreeGuidanceNet", "DiffusionVocoder", "MelSpectrogram",
-    "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "AdamW",
+    "DiffusionAR", "LTPlugin", "MultiResolutionSTFTLoss", "STFTLoss", "SumAndDifferenceSTFTLoss", "MelSTFTLoss", "AdamW",
     "RFDiffusion", "RFSampler", "LogitNormalDistribution",
     "KDiffusion", "KSampler", "KarrasSchedule", "LogNormalDistribution",
     "VRepainter", "RFRepainter", "KRepainter",

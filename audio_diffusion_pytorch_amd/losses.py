@@ -14,7 +14,8 @@
   LIN = mean |m_x - m_y|
   STFTLoss = w_sc SC + w_log_mag LM + w_lin_mag LIN;   MultiResolutionSTFTLoss = mean of the per-resolution values.
 
-auraloss's other options are accepted at their defaults only (any other value raises NotImplementedError naming it).
+auraloss's other options are accepted at their defaults only here (any other value raises NotImplementedError naming it);
+the mel scale, the perceptual pre-filter and the stereo sum/difference loss are in `spectral.py`, on kernels of their own.
 Only the input is differentiated: the gradient is the exact adjoint of the above, scaled by the incoming gradient read on
 the device.  No host synchronisation and no host->device copy, so a `VDiffusion` training step with this `loss_fn` is
 captured and replayed by graphed.py like the MSE step.

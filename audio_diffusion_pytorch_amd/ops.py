@@ -599,6 +599,46 @@ def stft_loss_bwd(x: Tensor, y: Tensor, gloss: Optional[Tensor], ws_fwd: Tensor,
     return dx
 
 
+def _spec_bins(res, n_bins) -> ctypes.Array:
+    """Filters per resolution (None: no filterbank) -> the host int64 array adp_spec_loss_* read at the call."""
+    return (ctypes.c_int64 * len(res))(*([0] * len(res) if n_bins is None else [int(v) for v in n_bins]))
+
+
+def spec_loss_fwd(x: Tensor, y: Tensor, pair: bool, res, n_bins, fb: Optional[Tensor], mel_range: Optional[Tensor],
+                  w_sc: float, w_log: float, w_lin: float, eps: float, w_sum: float = 1.0, w_diff: float = 1.0):
+    """adp_spec.h: the grouped / mel-scaled STFT loss of x against y ([..., L] rows; with `pair` consecutive rows are the two
+    channels of an item); returns (loss, forward workspace for spec_loss_bwd)."""
+    L = x.shape[-1]
+    rows, arr, bins = x.numel() // L, _stft_res(res), _spec_bins(res, n_bins)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    ws = _ws(_C.query("adp_spec_loss_ws_bytes", rows, L, int(pair), len(res), arr, bins, 0), x)
+    _C.call("adp_spec_loss_fwd", ptr(x), ptr(y), rows, L, int(pair), len(res), arr, bins, ptr(fb),
+            ptr(mel_range, torch.int32), w_sc, w_log, w_lin, eps, w_sum, w_diff, ptr(loss), ptr(ws), _C.stream())
+    return loss, ws
+
+
+def spec_loss_bwd(x: Tensor, y: Tensor, gloss: Optional[Tensor], ws_fwd: Tensor, pair: bool, res, n_bins,
+                  fb: Optional[Tensor], mel_range: Optional[Tensor], bin_range: Optional[Tensor], w_sc: float, w_log: float,
+                  w_lin: float, eps: float, w_sum: float = 1.0, w_diff: float = 1.0) -> Tensor:
+    L = x.shape[-1]
+    rows, arr, bins = x.numel() // L, _stft_res(res), _spec_bins(res, n_bins)
+    dx = torch.empty_like(x)
+    ws = _ws(_C.query("adp_spec_loss_ws_bytes", rows, L, int(pair), len(res), arr, bins, 1), x)
+    _C.call("adp_spec_loss_bwd", ptr(x), ptr(y), ptr(gloss), ptr(ws_fwd), rows, L, int(pair), len(res), arr, bins, ptr(fb),
+            ptr(mel_range, torch.int32), ptr(bin_range, torch.int32), w_sc, w_log, w_lin, eps, w_sum, w_diff, ptr(dx),
+            ptr(ws), _C.stream())
+    return dx
+
+
+def spec_fir(x: Tensor, taps: Tensor) -> Tensor:
+    """adp_spec_fir: every [..., L] row of x filtered by the odd-length taps, zero padded (F.conv1d(row, taps, padding=T // 2));
+    the adjoint is the call with the taps reversed."""
+    L = x.shape[-1]
+    out = torch.empty_like(x)
+    _C.call("adp_spec_fir", ptr(x), ptr(taps), x.numel() // L if L else 0, L, taps.numel(), ptr(out), _C.stream())
+    return out
+
+
 def v_step(x: Tensor, v: Tensor, ab4: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if out is None:
         out = torch.empty_like(x)

@@ -1,7 +1,11 @@
 """Multi-resolution STFT loss on the GPU (default resolutions at [4, 2, 2**18]): the native loss (adp_stft_loss_*) against
 the same contract written with torch.stft (hipFFT), and the replayed training step of the bench model with F.mse_loss,
 with the native loss and with the torch.stft loss (whether graphed.py captures that one).  Prints one JSON object.
-usage: python tools/stft_loss_bench.py [--steps K]"""
+--mode stereo measures the losses of spectral.py at the same shape instead: (a) the sum/difference loss in one native call
+against the two-call form (torch sum and difference, then losses.MultiResolutionSTFTLoss twice), alternating the two in one
+process, forward, backward and the replayed step; (b) the mel loss, and mel + A-weighting + sum/difference, against the same
+loss on torch.stft.
+usage: python tools/stft_loss_bench.py [--steps K] [--mode default|stereo]"""
 import argparse
 import json
 import os
@@ -16,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import audio_diffusion_pytorch_amd as adp  # noqa: E402
 from audio_diffusion_pytorch_amd import graphed, ops  # noqa: E402
+from audio_diffusion_pytorch_amd import spectral  # noqa: E402
 from audio_diffusion_pytorch_amd.losses import MultiResolutionSTFTLoss  # noqa: E402
 
 SHAPE = (4, 2, 2 ** 18)
@@ -42,6 +47,51 @@ class TorchSTFTLoss(torch.nn.Module):
             total = total + torch.linalg.vector_norm(my - mx) / torch.linalg.vector_norm(my) + \
                 (torch.log(mx) - torch.log(my)).abs().mean()
         return total / len(self.res)
+
+
+class TwoCallSumDiff(torch.nn.Module):
+    """Sum/difference without spectral.py: torch forms the two tensors, the native loss runs twice."""
+
+    def __init__(self):
+        super().__init__()
+        self.loss = MultiResolutionSTFTLoss()
+
+    def forward(self, x, y):
+        xs, xd, ys, yd = x[:, :1] + x[:, 1:], x[:, :1] - x[:, 1:], y[:, :1] + y[:, 1:], y[:, :1] - y[:, 1:]
+        return (self.loss(xs, ys) + self.loss(xd, yd)) / 2
+
+
+class TorchSpectralLoss(torch.nn.Module):
+    """The spectral.py contract on torch.stft: mel filterbank, optional FIR pre-filter, optional sum/difference."""
+
+    def __init__(self, sample_rate, n_bins, taps=None, pair=False, res=TorchSTFTLoss().res, eps=1e-8):
+        super().__init__()
+        self.res, self.eps, self.pair = res, eps, pair
+        for i, (N, _, _) in enumerate(res):
+            self.register_buffer(f"fb{i}", spectral.mel_filterbank(sample_rate, N, n_bins).float())
+        self.register_buffer("taps", None if taps is None else taps.view(1, 1, -1))
+
+    def forward(self, x, y):
+        L = x.shape[-1]
+
+        def groups(v):
+            gs = [v[:, 0] + v[:, 1], v[:, 0] - v[:, 1]] if self.pair else [v.reshape(-1, L)]
+            if self.taps is not None:
+                gs = [F.conv1d(g[:, None], self.taps, padding=self.taps.shape[-1] // 2)[:, 0] for g in gs]
+            return gs
+        values = []
+        for xg, yg in zip(groups(x), groups(y)):
+            total = 0.0
+            for i, (N, h, W) in enumerate(self.res):
+                win = torch.hann_window(W, device=x.device)
+                fb = getattr(self, f"fb{i}")
+                mx, my = (fb @ torch.sqrt(torch.clamp(s.real ** 2 + s.imag ** 2, min=self.eps)) for s in
+                          (torch.stft(v, N, h, W, win, center=True, pad_mode="reflect", return_complex=True)
+                           for v in (xg, yg)))
+                total = total + torch.linalg.vector_norm(my - mx) / torch.linalg.vector_norm(my) + \
+                    (torch.log(mx) - torch.log(my)).abs().mean()
+            values.append(total / len(self.res))
+        return sum(values) / len(values)
 
 
 def cuda_ms(fn, reps):
@@ -94,15 +144,58 @@ def step_ms(loss_fn, steps, dev):
     return out
 
 
+def stereo(args, dev, x, y):
+    """(a) one native sum/difference call against the two-call form, alternating, medians of `rounds`; (b) mel modes."""
+    res = {"shape": list(SHAPE), "mode": "stereo", "sample_rate": 44100, "n_bins": 64}
+    one, two = spectral.SumAndDifferenceSTFTLoss().to(dev), TwoCallSumDiff().to(dev)
+    la, lb = one(x, y).item(), two(x, y).item()
+    res["loss_one_call"], res["loss_two_calls"] = la, lb
+    times = {"one_call": [], "two_calls": []}
+    for _ in range(args.rounds):
+        for name, crit in (("one_call", one), ("two_calls", two)):
+            times[name].append(loss_times(crit, x, y, args.reps))
+    med = lambda v: sorted(v)[len(v) // 2]
+    for name, t in times.items():
+        f, b = med([a for a, _ in t]), med([c for _, c in t])
+        res[f"sumdiff_{name}_us"] = {"fwd": round(f, 1), "bwd": round(b, 1), "fwd_bwd": round(f + b, 1),
+                                     "fwd_bwd_min_max": [round(min(a + c for a, c in t), 1), round(max(a + c for a, c in t), 1)]}
+    kw = dict(scale="mel", sample_rate=44100, n_bins=64)
+    taps = spectral.a_weighting_fir(44100)
+    for name, native, ref in (("mel", spectral.MultiResolutionSTFTLoss(**kw), TorchSpectralLoss(44100, 64)),
+                              ("mel_aw_sumdiff", spectral.SumAndDifferenceSTFTLoss(perceptual_weighting=True, **kw),
+                               TorchSpectralLoss(44100, 64, taps, True))):
+        native, ref = native.to(dev), ref.to(dev)
+        nf, nb = loss_times(native, x, y, args.reps)
+        tf, tb = loss_times(ref, x, y, max(2, args.reps // 4))
+        res[f"{name}_native_us"] = {"fwd": round(nf, 1), "bwd": round(nb, 1), "fwd_bwd": round(nf + nb, 1)}
+        res[f"{name}_torch_stft_us"] = {"fwd": round(tf, 1), "bwd": round(tb, 1), "fwd_bwd": round(tf + tb, 1)}
+        res[f"loss_{name}_native"], res[f"loss_{name}_torch_stft"] = native(x, y).item(), ref(x, y).item()
+    del one, two, native, ref
+    torch.cuda.empty_cache()
+    steps = {"step_sumdiff_one_call": [], "step_sumdiff_two_calls": []}
+    for _ in range(2):   # alternating
+        steps["step_sumdiff_one_call"].append(step_ms(spectral.SumAndDifferenceSTFTLoss(), args.steps, dev))
+        steps["step_sumdiff_two_calls"].append(step_ms(TwoCallSumDiff(), args.steps, dev))
+    for name, runs in steps.items():
+        res[name] = dict(runs[-1], step_ms=min(r["step_ms"] for r in runs), step_ms_runs=[r["step_ms"] for r in runs])
+    res["step_mel_aw_sumdiff"] = step_ms(spectral.SumAndDifferenceSTFTLoss(perceptual_weighting=True, **kw), args.steps, dev)
+    res["step_mse"] = step_ms(F.mse_loss, args.steps, dev)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--mode", choices=("default", "stereo"), default="default")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     y = torch.randn(*SHAPE, device=dev, generator=g)
     x = y + 0.3 * torch.randn(*SHAPE, device=dev, generator=g)
+    if args.mode == "stereo":
+        return stereo(args, dev, x, y)
     native, ref = MultiResolutionSTFTLoss(), TorchSTFTLoss()
     res = {"shape": list(SHAPE), "resolutions": [list(r) for r in native.resolutions]}
     nf, nb = loss_times(native, x, y, args.reps)
