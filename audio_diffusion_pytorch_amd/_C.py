@@ -220,11 +220,20 @@ ABI["adp_spec.h"] = {
     "adp_spec_fir": (c_int, [P, P, I, I, I, P, P]),
 }
 
+# progressive distillation: the per-item combination (mid point, target) and the per-item weighted squared error
+ABI["adp_distill.h"] = {
+    "adp_distill_comb": (c_int, [P, P, P, P, I, I, I, P, P]),
+    "adp_distill_wmse_ws_bytes": (I, [I, I]),
+    "adp_distill_wmse_fwd": (c_int, [P, P, P, I, I, P, P, P]),
+    "adp_distill_wmse_bwd": (c_int, [P, P, P, P, I, I, P, P]),
+}
+
 
 # extension header -> the csrc/ file that includes and implements it (adp.h is implemented by all of them)
 HEADER_SOURCE = {"adp_ar.h": "elementwise.hip", "adp_lt.h": "lt.hip", "adp_enc.h": "encoder.hip", "adp_t5.h": "t5.hip",
                  "adp_rng.h": "rng.hip", "adp_clip.h": "clip.hip", "adp_gated.h": "gated.hip", "adp_sde.h": "sde.hip",
-                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip", "adp_repaint.h": "repaint.hip", "adp_spec.h": "spectral.hip"}
+                 "adp_rf.h": "rf.hip", "adp_edm.h": "edm.hip", "adp_repaint.h": "repaint.hip", "adp_spec.h": "spectral.hip",
+                 "adp_distill.h": "distill.hip"}
 
 # the whole C-ABI, name -> (restype, argtypes): what `_bind` binds and `call` / `call_value` / `query` resolve
 SIGNATURES = {}

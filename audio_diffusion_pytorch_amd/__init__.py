@@ -1,6 +1,7 @@
 """MI355X-native (gfx950, hand-written HIP) implementation of the audio-diffusion-pytorch denoising hot path.
 Exports mirror /root/reference/audio_diffusion_pytorch/__init__.py:1-20 for the in-scope symbols."""
 from .components import AppendChannelsPlugin, ClassifierFreeGuidanceNet, UNetV0
+from .distill import Distiller, VDistillation
 from .diffusion import (
     Diffusion,
     Distribution,
@@ -59,4 +60,5 @@ __all__ = [
     "RFDiffusion", "RFSampler", "LogitNormalDistribution",
     "KDiffusion", "KSampler", "KarrasSchedule", "LogNormalDistribution",
     "VRepainter", "RFRepainter", "KRepainter",
+    "VDistillation", "Distiller",
 ]

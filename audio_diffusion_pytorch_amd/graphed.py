@@ -13,8 +13,9 @@ sequence (one autograd node for the whole U-Net, no host reads), so `VDiffusion.
 the autograd node `_Replay` hands the flat buffer's per-parameter views to autograd, so AccumulateGrad, parameter hooks,
 gradient accumulation, `loss / k` scaling (the incoming gradient is a static input of graph B) and optimizers behave as in the
 eager step.  What is captured is exactly the eager path (`VDiffusion._forward_eager`), kernels and arithmetic unchanged.
-`ar.ARVDiffusion` and `rf.RFDiffusion` replay their steps through the same cache (they provide `loss_fn`,
-`sigma_distribution` and `_forward_eager`); `RFDiffusion` also accepts `rf.LogitNormalDistribution`, keyed on its `graph_key()`.
+`ar.ARVDiffusion`, `rf.RFDiffusion` and `distill.VDistillation` replay their steps through the same cache (they provide
+`loss_fn`, `sigma_distribution` and `_forward_eager`); `RFDiffusion` also accepts `rf.LogitNormalDistribution`, keyed on its
+`graph_key()`, and `VDistillation`'s stage (`distill.DistillSteps`) is keyed the same way.
 
 Taken only where it is safe, else the eager step runs as before (never an error): CUDA tensors, grad mode on, the stock
 `UniformDistribution` (for `RFDiffusion` also `LogitNormalDistribution`), inputs / conditioning tensors that do not require

@@ -6,6 +6,7 @@ the caller or with torch.empty on the input's device (PyTorch = device memory + 
 """
 import contextlib
 import ctypes
+import math
 import os
 from ctypes import byref
 from typing import Optional, Tuple
@@ -1219,6 +1220,78 @@ def repaint_step(objective: str, x: Tensor, p: Tensor, source: Tensor, mask_u8: 
     _C.call(entry, ptr(x), ptr(p), ptr(source), ptr(mask_u8, torch.uint8), ptr(row), rng, int(clip), ptr(scale), rows, per,
             ptr(out), _C.stream())
     return out
+
+
+# ---- include/adp_distill.h: progressive distillation (the per-item combination and the per-item weighted squared error)
+
+DISTILL_ROWS = ("sigma", "sigma_mid", "cos_d1", "neg_sin_d1", "c_x", "c_1", "c_2", "w")
+
+
+def distill_table(levels) -> Tensor:
+    """The rows [8, N] = (sigma_i, sigma_mid, cos d1, -sin d1, c_x, c_1, c_2, w_i) of the N student steps over the 2N + 1
+    teacher levels (include/adp_distill.h), float32 on the CPU: formed in float64 and rounded once.  With phi = level pi / 2,
+    d1 = phi_{2i} - phi_{2i+1}, d2 = phi_{2i+1} - phi_{2i+2}, D = d1 + d2: c_x = -sin d1 sin d2 / sin D,
+    c_1 = cos d2 sin d1 / sin D, c_2 = sin d2 / sin D, and w_i = max(cos^2 phi_{2i}, sin^2 phi_{2i}): the truncated-SNR weight
+    max(SNR, 1) on the x error of Salimans & Ho 2022, written on the v error (|dx|^2 = sin^2 phi |dv|^2)."""
+    s = torch.as_tensor(levels).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    if s.numel() < 3 or s.numel() % 2 == 0:
+        raise ValueError(f"distill_table: levels holds the 2N + 1 teacher levels of N >= 1 student steps; got {s.numel()}")
+    if not bool(((s >= 0) & (s <= 1)).all()) or not bool((s[1:] < s[:-1]).all()):
+        raise ValueError("distill_table: the levels must fall strictly inside [0, 1]")
+    half = math.pi / 2
+    d1, d2 = (s[0:-2:2] - s[1:-1:2]) * half, (s[1:-1:2] - s[2::2]) * half
+    sin_d = torch.sin(d1 + d2)
+    phi = s[0:-2:2] * half
+    w = torch.maximum(torch.cos(phi) ** 2, torch.sin(phi) ** 2)
+    rows = [s[0:-2:2], s[1:-1:2], torch.cos(d1), -torch.sin(d1), -torch.sin(d1) * torch.sin(d2) / sin_d,
+            torch.cos(d2) * torch.sin(d1) / sin_d, torch.sin(d2) / sin_d, w]
+    return torch.stack(rows, dim=0).to(torch.float32).contiguous()
+
+
+def distill_comb(x: Tensor, p: Tensor, coef: Tensor, q: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """out = c0_r x + c1_r p [+ c2_r q] on x [B, ...] with one coefficient per item and term, coef [terms, B] float32 on the
+    device, terms = 2 (no q) or 3 (adp_distill_comb).  `out` may be any input."""
+    rows, per = _item_dims("distill_comb", x)
+    for name, other in (("p", p), ("q", q), ("out", out)):
+        if other is not None and other.shape != x.shape:
+            raise ValueError(f"distill_comb: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    terms = 2 if q is None else 3
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (terms, rows):
+        raise ValueError(f"distill_comb: coef holds {terms} float32 coefficients per item, [{terms}, {rows}]"
+                         f"{'' if q is not None else ' (no q: two terms)'}; got {coef.dtype} {tuple(coef.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    _C.call("adp_distill_comb", ptr(x), ptr(p), ptr(q), ptr(coef), terms, rows, per, ptr(out), _C.stream())
+    return out
+
+
+def _check_wmse(what: str, v_pred: Tensor, v_target: Tensor, w: Optional[Tensor]) -> Tuple[int, int]:
+    rows, per = _item_dims(what, v_pred)
+    if v_target.shape != v_pred.shape:
+        raise ValueError(f"{what}: v_target must have v_pred's shape {tuple(v_pred.shape)}; got {tuple(v_target.shape)}")
+    if w is not None and (w.dtype != torch.float32 or w.numel() != rows):
+        raise ValueError(f"{what}: w holds one float32 weight per item ({rows}); got {w.dtype} {tuple(w.shape)}")
+    if rows * per == 0:
+        raise ValueError(f"{what}: the mean over no elements is undefined")
+    return rows, per
+
+
+def distill_wmse_fwd(v_pred: Tensor, v_target: Tensor, w: Optional[Tensor] = None) -> Tensor:
+    """loss = mean over all elements of w_r (v_pred - v_target)^2, one weight per item (w=None: ones), in a fixed order of
+    summation (adp_distill_wmse_fwd)."""
+    rows, per = _check_wmse("distill_wmse_fwd", v_pred, v_target, w)
+    loss = torch.empty((), dtype=torch.float32, device=v_pred.device)
+    ws = _ws(_C.query("adp_distill_wmse_ws_bytes", rows, per), v_pred)
+    _C.call("adp_distill_wmse_fwd", ptr(v_pred), ptr(v_target), ptr(w), rows, per, ptr(loss), ptr(ws), _C.stream())
+    return loss
+
+
+def distill_wmse_bwd(v_pred: Tensor, v_target: Tensor, w: Optional[Tensor], gloss: Optional[Tensor]) -> Tensor:
+    """dv = gloss * 2 * w_r * (v_pred - v_target) / numel (adp_distill_wmse_bwd); gloss=None: 1."""
+    rows, per = _check_wmse("distill_wmse_bwd", v_pred, v_target, w)
+    dv = torch.empty_like(v_pred)
+    _C.call("adp_distill_wmse_bwd", ptr(v_pred), ptr(v_target), ptr(w), ptr(gloss), rows, per, ptr(dv), _C.stream())
+    return dv
 
 
 def cfg_mix(y2: Tensor, scale: float) -> Tensor:
