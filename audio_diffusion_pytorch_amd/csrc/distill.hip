@@ -3,11 +3,9 @@
 //   adp_distill_comb     : out = c0 x + c1 p [+ c2 q]                          2 or 3 reads, 1 write
 //   adp_distill_wmse_fwd : loss = (1 / n) sum_r w_r sum_e (pred - target)^2    2 reads; partials, then one final block
 //   adp_distill_wmse_bwd : dv = (gloss 2 / n) w_r (pred - target)              2 reads, 1 write
-// All are bandwidth-bound elementwise passes of rf_noise_kernel's shape (rf.hip): one thread owns one group of four elements
-// per pass, in a grid-stride loop over the groups; 16-byte accesses where every tensor operand allows them, single elements
-// otherwise.  The per-item values (coefficients, weights) are found by item_values4.  No atomics; the one use of LDS is the
-// block sum of the loss partials (adp_block_sum, as adp_mse_fwd's); ordinary vector or single-element stores only.  The walk,
-// the grid and the host checks are csrc/sampler_update.h's.
+// The combination is a pass of csrc/sampler_update.h's for_groups4.  The two loss kernels write the same pass out (through
+// for_groups4 their unweighted forms measured outside the parent's spread) and are kept in step with it by hand; the one use
+// of LDS is the block sum of the loss partials (adp_block_sum, as adp_mse_fwd's).  The host checks are that header's too.
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_distill.h"
@@ -29,31 +27,23 @@ template <bool THREE, bool VEC>
 __global__ __launch_bounds__(256) void distill_comb_kernel(const float* x, const float* p, const float* q,
                                                            const float* coef, int64_t rows, int64_t n, int64_t per,
                                                            float* out) {
-  const int64_t groups = groups4(n);
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
-    const int64_t e = 4 * g;
-    float c0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, c1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, c2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    item_values4(coef, e, n, per, c0);
-    item_values4(coef + rows, e, n, per, c1);
-    if (THREE) item_values4(coef + 2 * rows, e, n, per, c2);
-    if (VEC && e + 4 <= n) {
-      const f32x4 xv = *(const f32x4*)(x + e), pv = *(const f32x4*)(p + e);
-      f32x4 qv = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (THREE) qv = *(const f32x4*)(q + e);
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = comb_elem<THREE>(c0[k], c1[k], c2[k], xv[k], pv[k], qv[k]);
-      *(f32x4*)(out + e) = o;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (e + k < n) {
-          const float qv = THREE ? q[e + k] : 0.0f;  // (every operand read before the store: aliasing)
-          const float xv = x[e + k], pv = p[e + k];
-          out[e + k] = comb_elem<THREE>(c0[k], c1[k], c2[k], xv, pv, qv);
-        }
-    }
-  }
+  const In in[] = {x, p, {q, THREE}};
+  const Out outs[] = {out};
+  struct Group {
+    float c0[4], c1[4], c2[4];
+  };
+  for_groups4<VEC>(
+      in, outs, n,
+      [&](int64_t, int64_t e, bool) {
+        Group c{{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+        item_values4(coef, e, n, per, c.c0);
+        item_values4(coef + rows, e, n, per, c.c1);
+        if (THREE) item_values4(coef + 2 * rows, e, n, per, c.c2);
+        return c;
+      },
+      [&](const Group& c, int k, const float(&a)[3], float(&o)[1]) {
+        o[0] = comb_elem<THREE>(c.c0[k], c.c1[k], c.c2[k], a[0], a[1], a[2]);
+      });
 }
 
 // ---- the weighted squared error.  A lane adds its elements in element order, pass by pass: the 16-byte and the
@@ -139,15 +129,11 @@ inline int wmse_blocks(int64_t n) {
 
 extern "C" int adp_distill_comb(const float* x, const float* p, const float* q, const float* coef, int64_t terms,
                                 int64_t rows, int64_t per, float* out, void* stream) {
-  if (!x || !p || !coef || !out) return ADP_ERR_NULL;
   if (terms == 3 && !q) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0 || (terms != 2 && terms != 3) || (terms == 2 && q)) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(x, 4) || misaligned(p, 4) || (q && misaligned(q, 4)) || misaligned(coef, 4) || misaligned(out, 4))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(x, 16) && !misaligned(p, 16) && (!q || !misaligned(q, 16)) && !misaligned(out, 16);
+  const bool own_ok = (terms == 2 || terms == 3) && !(terms == 2 && q);
+  const int64_t n = flat_count({x, p, coef, out}, {q}, rows, per, own_ok);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({x, p, q, out});
   with_flag(terms == 3, [&](auto THREE) {
     with_flag(vec, [&](auto VEC) {
       ADP_LAUNCH((distill_comb_kernel<THREE(), VEC()>), dim3(grid4(n)), dim3(256), stream, x, p, q, coef, rows, n, per, out);
@@ -163,15 +149,9 @@ extern "C" int64_t adp_distill_wmse_ws_bytes(int64_t rows, int64_t per) {
 
 extern "C" int adp_distill_wmse_fwd(const float* v_pred, const float* v_target, const float* w, int64_t rows, int64_t per,
                                     float* loss, float* ws, void* stream) {
-  if (!v_pred || !v_target || !loss || !ws) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(v_pred, 4) || misaligned(v_target, 4) || (w && misaligned(w, 4)) || misaligned(loss, 4) ||
-      misaligned(ws, 4))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(v_pred, 16) && !misaligned(v_target, 16);
+  const int64_t n = flat_count({v_pred, v_target, loss, ws}, {w}, rows, per);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({v_pred, v_target});
   const int nb = wmse_blocks(n);
   with_flag(w != nullptr, [&](auto WEIGHTED) {
     with_flag(vec, [&](auto VEC) {
@@ -185,15 +165,9 @@ extern "C" int adp_distill_wmse_fwd(const float* v_pred, const float* v_target, 
 
 extern "C" int adp_distill_wmse_bwd(const float* v_pred, const float* v_target, const float* w, const float* gloss,
                                     int64_t rows, int64_t per, float* dv, void* stream) {
-  if (!v_pred || !v_target || !dv) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(v_pred, 4) || misaligned(v_target, 4) || (w && misaligned(w, 4)) || (gloss && misaligned(gloss, 4)) ||
-      misaligned(dv, 4))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(v_pred, 16) && !misaligned(v_target, 16) && !misaligned(dv, 16);
+  const int64_t n = flat_count({v_pred, v_target, dv}, {w, gloss}, rows, per);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({v_pred, v_target, dv});
   with_flag(w != nullptr, [&](auto WEIGHTED) {
     with_flag(vec, [&](auto VEC) {
       ADP_LAUNCH((distill_wmse_bwd_kernel<WEIGHTED(), VEC()>), dim3(grid4(n)), dim3(256), stream, v_pred, v_target, w,

@@ -3,13 +3,10 @@
 //   adp_edm_noise : x_in = c_in x + (c_in sigma) n ; target = (sigma / (sd r)) x - (sd / r) n              2 reads, 2 writes
 //   adp_edm_step  : xs_out = c1 clip(a0 xs - b0 F) + d1 (e0 xs + f0 F) [+ cb (x0c - hist)] [+ s1 z]        2 reads, 1 write
 //                                                                                                 (order 2: 3 reads, 2 writes)
-// Both are bandwidth-bound elementwise passes of rf_step_kernel's shape (rf.hip): one thread owns one group of four elements
-// per pass, in a grid-stride loop over the groups; 16-byte accesses where every tensor operand allows them, single elements
-// otherwise.  The per-item values (sigma, scale) are found by one 64-bit division per group and a walk over the item
-// boundaries inside it (item_values4); the noise z is formed in registers from the row of include/adp_rng.h, one Philox
-// call and two Box-Muller pairs per group (philox.h), as in sde.hip.  No LDS, no atomics, no cross-lane traffic; ordinary
-// vector or single-element stores only.  The arithmetic of x0 and its clamps, the walk and the grid are
-// csrc/sampler_update.h's, shared with clip.hip, sde.hip and rf.hip.
+// The noising is a pass of csrc/sampler_update.h's for_groups4.  The step writes the same pass out, with the same
+// guarantees and that header's draw: through for_groups4 its CLIP_SCALE, ORDER 2, VEC form needs more scalar registers than
+// there are.  That loop is kept in step with for_groups4 by hand.  The arithmetic of x0 and its clamps is that header's
+// too, shared with clip.hip, sde.hip and rf.hip.
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_edm.h"
@@ -18,7 +15,6 @@
 
 namespace {
 
-using namespace philox;
 using namespace upd;
 
 // ---- noising.  The four per-item coefficients by the sequence of the header: one product, one fused multiply-add, one
@@ -52,38 +48,29 @@ __device__ __forceinline__ EdmNoised edm_noise_elem(const EdmNoiseCoef& c, float
 template <bool VEC>
 __global__ __launch_bounds__(256) void edm_noise_kernel(const float* x, const float* noise, const float* sigma, float sd,
                                                         int64_t n, int64_t per, float* xi, float* tg) {
-  const int64_t groups = groups4(n);
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
-    const int64_t e = 4 * g;
-    float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    item_values4(sigma, e, n, per, sv);
-    // the coefficients are a function of the item's sigma alone: formed for the group's first element and again only where
-    // the walk met another value (a NaN sigma compares unequal and is formed again: the same NaN coefficients)
+  const In in[] = {x, noise};
+  const Out out[] = {xi, tg};
+  struct Group {
     EdmNoiseCoef c[4];
-    c[0] = edm_noise_coef(sv[0], sd);
+  };
+  for_groups4<VEC>(
+      in, out, n,
+      [&](int64_t, int64_t e, bool) {
+        float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        item_values4(sigma, e, n, per, sv);
+        // the coefficients are a function of the item's sigma alone: formed for the group's first element and again only
+        // where the walk met another value (a NaN sigma compares unequal and is formed again: the same NaN coefficients)
+        Group v;
+        v.c[0] = edm_noise_coef(sv[0], sd);
 #pragma unroll
-    for (int k = 1; k < 4; ++k) c[k] = sv[k] == sv[k - 1] ? c[k - 1] : edm_noise_coef(sv[k], sd);
-    if (VEC && e + 4 <= n) {
-      const f32x4 xv = *(const f32x4*)(x + e), nv = *(const f32x4*)(noise + e);
-      f32x4 a, b;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const EdmNoised r = edm_noise_elem(c[k], xv[k], nv[k]);
-        a[k] = r.x_in;
-        b[k] = r.target;
-      }
-      *(f32x4*)(xi + e) = a;
-      *(f32x4*)(tg + e) = b;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (e + k < n) {
-          const EdmNoised r = edm_noise_elem(c[k], x[e + k], noise[e + k]);  // (both read before either store: aliasing)
-          xi[e + k] = r.x_in;
-          tg[e + k] = r.target;
-        }
-    }
-  }
+        for (int k = 1; k < 4; ++k) v.c[k] = sv[k] == sv[k - 1] ? v.c[k - 1] : edm_noise_coef(sv[k], sd);
+        return v;
+      },
+      [&](const Group& v, int k, const float(&a)[2], float(&o)[2]) {
+        const EdmNoised r = edm_noise_elem(v.c[k], a[0], a[1]);
+        o[0] = r.x_in;
+        o[1] = r.target;
+      });
 }
 
 // ---- the sampler update: edm_step_elem of sampler_update.h behind x0 = clip_x0(...)
@@ -95,21 +82,12 @@ __global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const flo
   const EdmCoef c{coef8[0], coef8[1], coef8[2], coef8[3], coef8[4], coef8[5], coef8[6], coef8[7]};
   const bool multi = ORDER == 2 && c.cb != 0.0f;  // (the same branches in every lane of the launch)
   const bool noisy = c.s1 != 0.0f;
-  RngRow row{0u, 0u, 0u};
-  if (noisy && rng4) row = rng_row(rng4);
-  const float nan = __uint_as_float(0x7FC00000u);
+  const Normals normals(rng4, noisy);
   const int64_t groups = groups4(n);
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
     const int64_t e = 4 * g;
     f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (noisy) {
-      if (rng4) {
-        z = rng_normal4(row, g);
-      } else {
-        const f32x4 z_nan = {nan, nan, nan, nan};  // noise asked for without a row: loud, and nothing is dereferenced
-        z = z_nan;
-      }
-    }
+    if (noisy) z = normals(g);
     float s[4] = {1.0f, 1.0f, 1.0f, 1.0f};
     if (CLIP == CLIP_SCALE) item_values4(scale, e, n, per, s);
     if (VEC && e + 4 <= n) {
@@ -145,15 +123,9 @@ __global__ __launch_bounds__(256) void edm_step_kernel(const float* x, const flo
 
 extern "C" int adp_edm_noise(const float* x, const float* noise, const float* sigma, float sigma_data, int64_t rows,
                              int64_t per, float* x_in_out, float* target_out, void* stream) {
-  if (!x || !noise || !sigma || !x_in_out || !target_out) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0 || !(sigma_data > 0.0f)) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(x, 4) || misaligned(noise, 4) || misaligned(sigma, 4) || misaligned(x_in_out, 4) ||
-      misaligned(target_out, 4))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(x, 16) && !misaligned(noise, 16) && !misaligned(x_in_out, 16) && !misaligned(target_out, 16);
+  const int64_t n = flat_count({x, noise, sigma, x_in_out, target_out}, {}, rows, per, sigma_data > 0.0f);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({x, noise, x_in_out, target_out});
   with_flag(vec, [&](auto VEC) {
     ADP_LAUNCH((edm_noise_kernel<VEC()>), dim3(grid4(n)), dim3(256), stream, x, noise, sigma, sigma_data, n, per, x_in_out,
                target_out);
@@ -164,24 +136,12 @@ extern "C" int adp_edm_noise(const float* x, const float* noise, const float* si
 extern "C" int adp_edm_step(const float* xs, const float* f, const float* hist, const float* coef8, const uint32_t* rng4,
                             int64_t order, int64_t clip, const float* scale, int64_t rows, int64_t per, float* xs_out,
                             float* hist_out, void* stream) {
-  if (!xs || !f || !coef8 || !xs_out) return ADP_ERR_NULL;
   if (order == 2 && (!hist || !hist_out)) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0 || (order != 1 && order != 2) || (clip != 0 && clip != 1) || (clip == 0 && scale))
-    return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(xs, 4) || misaligned(f, 4) || misaligned(coef8, 4) || misaligned(xs_out, 4) ||
-      (rng4 && misaligned(rng4, 4)) || (scale && misaligned(scale, 4)) ||
-      (order == 2 && (misaligned(hist, 4) || misaligned(hist_out, 4))))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  bool vec = !misaligned(xs, 16) && !misaligned(f, 16) && !misaligned(xs_out, 16);
-  if (order == 2) {
-    vec = vec && !misaligned(hist, 16) && !misaligned(hist_out, 16);
-  } else {  // (the first-order kernels take no history)
-    hist = nullptr;
-    hist_out = nullptr;
-  }
+  if (order != 2) hist = nullptr, hist_out = nullptr;  // (the first-order kernels take no history)
+  const bool own_ok = (order == 1 || order == 2) && clip_ok(clip, scale);
+  const int64_t n = flat_count({xs, f, coef8, xs_out}, {rng4, scale, hist, hist_out}, rows, per, own_ok);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({xs, f, xs_out, hist, hist_out});
   with_clip(clip, scale, [&](auto CLIP) {
     with_flag(order == 2, [&](auto ORDER2) {
       with_flag(vec, [&](auto VEC) {

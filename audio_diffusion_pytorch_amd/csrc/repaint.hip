@@ -1,13 +1,10 @@
 // RePaint inpainting (include/adp_repaint.h): one resample of VRepainter / RFRepainter / KRepainter behind the net.
 //   adp_repaint_{v,rf,k}_step : y = the objective's first-order update of (x, p) ; y = A y + S z (the jump back) ;
 //                               x_out = mask ? P source + Q z : y                      3 reads + 1 byte, 1 write
-// A bandwidth-bound elementwise pass of rf_step_kernel's shape (rf.hip): one thread owns one group of four elements per
-// pass, in a grid-stride loop over the groups; 16-byte accesses where every float operand allows them and the mask is
-// 4-byte aligned (its four bytes are then one word), single elements otherwise.  The per-item scale is found by one 64-bit
-// division per group and a walk over the item boundaries inside it (item_values4); the noise z is formed in registers from
-// the row of include/adp_rng.h, one Philox call and two Box-Muller pairs per group (philox.h), and only by the groups that
-// need it.  No LDS, no atomics, no cross-lane traffic; ordinary vector or single-element stores only.  The three updates are
-// csrc/sampler_update.h's (the ones sde.hip, rf.hip and edm.hip launch) and inpaint_blend.h's rotation (adp_v_step's bits).
+// The pass of csrc/sampler_update.h's for_groups4, written out with the same guarantees (through for_groups4 the CLIP_SCALE
+// forms need more scalar registers than there are) and kept in step with it by hand, with that header's draw, made only by the groups that need it.  A whole
+// group also needs a 4-byte aligned mask, whose four bytes are then one word.  The three updates are that header's (the ones
+// sde.hip, rf.hip and edm.hip launch) and inpaint_blend.h's rotation (adp_v_step's bits).
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_repaint.h"
@@ -17,7 +14,6 @@
 
 namespace {
 
-using namespace philox;
 using namespace upd;
 
 enum { OBJ_V = 0, OBJ_RF = 1, OBJ_K = 2 };
@@ -93,9 +89,7 @@ __global__ __launch_bounds__(256) void repaint_step_kernel(const float* x, const
                                                            const float* scale, int64_t n, int64_t per, float* xo) {
   const Step<OBJ> st(row);
   const Blend b(row + Step<OBJ>::WORDS);  // (the same branches in every lane of the launch)
-  RngRow r{0u, 0u, 0u};
-  if ((b.jump || b.renoise) && rng4) r = rng_row(rng4);
-  const float nan = __uint_as_float(0x7FC00000u);
+  const Normals normals(rng4, b.jump || b.renoise);
   const int64_t groups = groups4(n);
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
     const int64_t e = 4 * g;
@@ -112,14 +106,7 @@ __global__ __launch_bounds__(256) void repaint_step_kernel(const float* x, const
     }
     // a group draws only if it needs a normal: the jump does everywhere, the known region where an element keeps the source
     f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (b.jump || (b.renoise && (keep[0] || keep[1] || keep[2] || keep[3]))) {
-      if (rng4) {
-        z = rng_normal4(r, g);
-      } else {
-        const f32x4 z_nan = {nan, nan, nan, nan};  // noise asked for without a row: loud, and nothing is dereferenced
-        z = z_nan;
-      }
-    }
+    if (b.jump || (b.renoise && (keep[0] || keep[1] || keep[2] || keep[3]))) z = normals(g);
     float s[4] = {1.0f, 1.0f, 1.0f, 1.0f};
     if (CLIP == CLIP_SCALE) item_values4(scale, e, n, per, s);
     if (whole) {
@@ -141,16 +128,10 @@ template <int OBJ>
 int repaint_step(const float* x, const float* p, const float* source, const uint8_t* mask, const float* row,
                  const uint32_t* rng4, int64_t clip, const float* scale, int64_t rows, int64_t per, float* x_out,
                  void* stream) {
-  if (!x || !p || !source || !mask || !row || !x_out) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0 || (clip != 0 && clip != 1) || (clip == 0 && scale)) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(x, 4) || misaligned(p, 4) || misaligned(source, 4) || misaligned(row, 4) || misaligned(x_out, 4) ||
-      (rng4 && misaligned(rng4, 4)) || (scale && misaligned(scale, 4)))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(x, 16) && !misaligned(p, 16) && !misaligned(source, 16) && !misaligned(x_out, 16) &&
-                   !misaligned(mask, 4);
+  if (!mask) return ADP_ERR_NULL;  // (bytes: no alignment of its own)
+  const int64_t n = flat_count({x, p, source, row, x_out}, {rng4, scale}, rows, per, clip_ok(clip, scale));
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({x, p, source, x_out}) && !misaligned(mask, 4);
   with_clip(clip, scale, [&](auto CLIP) {
     with_flag(vec, [&](auto VEC) {
       ADP_LAUNCH((repaint_step_kernel<OBJ, CLIP(), VEC()>), dim3(grid4(n)), dim3(256), stream, x, p, source, mask, row,

@@ -1,12 +1,9 @@
 // Rectified flow (include/adp_rf.h): the fused noising of the training step and the sampler update.
 //   adp_rf_noise : x_t = (1 - t_r) x + t_r n ; u = n - x                                  2 reads, 2 writes
 //   adp_rf_step  : x_out = c1 clip(a0 x - b0 u) + a1 (c0 u + x) [+ cb (w - hist)]         2 reads, 1 write (order 2: 3, 2)
-// Both are bandwidth-bound elementwise passes of v_step_eta_kernel's shape (sde.hip): one thread owns one group of four
-// elements per pass, in a grid-stride loop over the groups; 16-byte accesses where every tensor operand allows them, single
-// elements otherwise.  The per-item values (t, scale) are found by one 64-bit division per group and a walk over the item
-// boundaries inside it (item_values4).  No LDS, no atomics, no cross-lane traffic; ordinary vector or single-element stores
-// only.  The arithmetic of x0 and its clamps, the walk and the grid are csrc/sampler_update.h's, shared with clip.hip and
-// sde.hip.
+// Both write out the pass of csrc/sampler_update.h's for_groups4, which states the geometry and its guarantees, and are
+// kept in step with it by hand: through for_groups4 the noising measured up to 3 % and the step's order-2 forms up to 1.5 %
+// slower.  The arithmetic of x0 and its clamps and the host checks are that header's too, shared with clip.hip and sde.hip.
 #include "adp_rt.h"
 #include "adp.h"
 #include "adp_rf.h"
@@ -103,14 +100,9 @@ __global__ __launch_bounds__(256) void rf_step_kernel(const float* x, const floa
 
 extern "C" int adp_rf_noise(const float* x, const float* noise, const float* t, int64_t rows, int64_t per, float* x_t_out,
                             float* u_out, void* stream) {
-  if (!x || !noise || !t || !x_t_out || !u_out) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0) return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(x, 4) || misaligned(noise, 4) || misaligned(t, 4) || misaligned(x_t_out, 4) || misaligned(u_out, 4))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  const bool vec = !misaligned(x, 16) && !misaligned(noise, 16) && !misaligned(x_t_out, 16) && !misaligned(u_out, 16);
+  const int64_t n = flat_count({x, noise, t, x_t_out, u_out}, {}, rows, per);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({x, noise, x_t_out, u_out});
   with_flag(vec, [&](auto VEC) {
     ADP_LAUNCH((rf_noise_kernel<VEC()>), dim3(grid4(n)), dim3(256), stream, x, noise, t, n, per, x_t_out, u_out);
   });
@@ -120,23 +112,12 @@ extern "C" int adp_rf_noise(const float* x, const float* noise, const float* t, 
 extern "C" int adp_rf_step(const float* x, const float* u, const float* hist, const float* coef6, int64_t order,
                            int64_t clip, const float* scale, int64_t rows, int64_t per, float* x_out, float* hist_out,
                            void* stream) {
-  if (!x || !u || !coef6 || !x_out) return ADP_ERR_NULL;
   if (order == 2 && (!hist || !hist_out)) return ADP_ERR_NULL;
-  if (rows < 0 || per < 0 || (order != 1 && order != 2) || (clip != 0 && clip != 1) || (clip == 0 && scale))
-    return ADP_ERR_SHAPE;
-  if (count_overflows(rows, per)) return ADP_ERR_SHAPE;
-  if (misaligned(x, 4) || misaligned(u, 4) || misaligned(coef6, 4) || misaligned(x_out, 4) ||
-      (scale && misaligned(scale, 4)) || (order == 2 && (misaligned(hist, 4) || misaligned(hist_out, 4))))
-    return ADP_ERR_ALIGN;
-  const int64_t n = rows * per;
-  if (n == 0) return ADP_OK;
-  bool vec = !misaligned(x, 16) && !misaligned(u, 16) && !misaligned(x_out, 16);
-  if (order == 2) {
-    vec = vec && !misaligned(hist, 16) && !misaligned(hist_out, 16);
-  } else {  // (the first-order kernels take no history)
-    hist = nullptr;
-    hist_out = nullptr;
-  }
+  if (order != 2) hist = nullptr, hist_out = nullptr;  // (the first-order kernels take no history)
+  const bool own_ok = (order == 1 || order == 2) && clip_ok(clip, scale);
+  const int64_t n = flat_count({x, u, coef6, x_out}, {scale, hist, hist_out}, rows, per, own_ok);
+  if (n <= 0) return (int)n;
+  const bool vec = aligned16({x, u, x_out, hist, hist_out});
   with_clip(clip, scale, [&](auto CLIP) {
     with_flag(order == 2, [&](auto ORDER2) {
       with_flag(vec, [&](auto VEC) {

@@ -828,6 +828,36 @@ def _check_clip(what: str, clip, scale, rows: int) -> None:
             raise ValueError(f"{what}: scale must hold one value per item ({rows}); got {scale.numel()}")
 
 
+def _check_like(what: str, x: Tensor, x_name: str = "x", **tensors) -> None:
+    """Every named tensor that is given has x's shape."""
+    for name, t in tensors.items():
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"{what}: {name} must have {x_name}'s shape {tuple(x.shape)}; got {tuple(t.shape)}")
+
+
+def _check_f32(what: str, t: Tensor, n: int, holds: str) -> None:
+    """t holds n float32 values; `holds` names it and them."""
+    if t.dtype != torch.float32 or t.numel() != n:
+        raise ValueError(f"{what}: {holds}; got {t.dtype} {tuple(t.shape)}")
+
+
+def _check_order(what: str, order, clip, scale, rows: int, hist, hist_out) -> None:
+    """order is 1 or 2; then the clip / scale arguments (`_check_clip`); then the history arguments fit the order."""
+    if order not in (1, 2) or isinstance(order, bool):
+        raise ValueError(f"{what}: order must be 1 or 2; got {order!r}")
+    _check_clip(what, clip, scale, rows)
+    if order == 1:
+        if hist is not None or hist_out is not None:
+            raise ValueError(f"{what}: the first-order step has no history")
+    elif hist is None:
+        raise ValueError(f"{what}: the second-order step needs hist")
+
+
+def _like(x: Tensor, out: Optional[Tensor]) -> Tensor:
+    """`out`, or a new tensor like x when it is missing."""
+    return torch.empty_like(x) if out is None else out
+
+
 def clip_rank(q: float, per: int) -> Tuple[int, float]:
     """(lo, w) of torch.quantile's linear rule, in its float32 arithmetic: rank = float32(q) * float32(per - 1)."""
     if not 0.0 <= q <= 1.0:
@@ -930,16 +960,11 @@ def v_step_eta(x: Tensor, v: Tensor, coef5: Tensor, rng4: Optional[Tensor], scal
     to [-1, 1]); eps comes from the raw v.  A row with cz = 0 does not read rng4, which may then be None (with cz != 0 a
     missing row gives NaN).  `out` may be x."""
     rows, per = _item_dims("v_step_eta", x)
-    for name, t in (("v", v), ("out", out)):
-        if t is not None and t.shape != x.shape:
-            raise ValueError(f"v_step_eta: {name} must have x's shape {tuple(x.shape)}; got {tuple(t.shape)}")
-    if coef5.dtype != torch.float32 or coef5.numel() != 5:
-        raise ValueError(f"v_step_eta: coef5 holds five float32 values (a0, b0, a1, ce, cz); got {coef5.dtype} "
-                         f"{tuple(coef5.shape)}")
+    _check_like("v_step_eta", x, v=v, out=out)
+    _check_f32("v_step_eta", coef5, 5, "coef5 holds five float32 values (a0, b0, a1, ce, cz)")
     _check_clip("v_step_eta", clip, scale, rows)
     row = None if rng4 is None else _rng_row_ptr("v_step_eta", rng4)
-    if out is None:
-        out = torch.empty_like(x)
+    out = _like(x, out)
     _C.call("adp_v_step_eta", ptr(x), ptr(v), ptr(coef5), row, int(clip), ptr(scale), rows, per, ptr(out), _C.stream())
     return out
 
@@ -950,15 +975,9 @@ def rf_noise(x: Tensor, noise: Tensor, t: Tensor, x_t_out: Optional[Tensor] = No
     """(x_t, u) = ((1 - t_r) x + t_r noise, noise - x) for x [B, ...] and one time per item, t [B] (adp_rf_noise).  t = 0
     returns x and t = 1 returns noise, bit for bit.  An output may be an input."""
     rows, per = _item_dims("rf_noise", x)
-    for name, other in (("noise", noise), ("x_t_out", x_t_out), ("u_out", u_out)):
-        if other is not None and other.shape != x.shape:
-            raise ValueError(f"rf_noise: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
-    if t.dtype != torch.float32 or t.numel() != rows:
-        raise ValueError(f"rf_noise: t holds one float32 time per item ({rows}); got {t.dtype} {tuple(t.shape)}")
-    if x_t_out is None:
-        x_t_out = torch.empty_like(x)
-    if u_out is None:
-        u_out = torch.empty_like(x)
+    _check_like("rf_noise", x, noise=noise, x_t_out=x_t_out, u_out=u_out)
+    _check_f32("rf_noise", t, rows, f"t holds one float32 time per item ({rows})")
+    x_t_out, u_out = _like(x, x_t_out), _like(x, u_out)
     _C.call("adp_rf_noise", ptr(x), ptr(noise), ptr(t), rows, per, ptr(x_t_out), ptr(u_out), _C.stream())
     return x_t_out, u_out
 
@@ -992,24 +1011,12 @@ def rf_step(x: Tensor, u: Tensor, coef6: Tensor, scale: Optional[Tensor] = None,
     eps comes from the raw u.  order=1 returns x_next and has no history; order=2 returns (x_next, w) and needs `hist` (the
     previous step's w), which a row with cb = 0 does not read.  Every output may be its input."""
     rows, per = _item_dims("rf_step", x)
-    for name, other in (("u", u), ("hist", hist), ("out", out), ("hist_out", hist_out)):
-        if other is not None and other.shape != x.shape:
-            raise ValueError(f"rf_step: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
-    if coef6.dtype != torch.float32 or coef6.numel() != 6:
-        raise ValueError(f"rf_step: coef6 holds six float32 values (1, t0, 1 - t0, t1, 1 - t1, cb); got {coef6.dtype} "
-                         f"{tuple(coef6.shape)}")
-    if order not in (1, 2) or isinstance(order, bool):
-        raise ValueError(f"rf_step: order must be 1 or 2; got {order!r}")
-    _check_clip("rf_step", clip, scale, rows)
-    if order == 1:
-        if hist is not None or hist_out is not None:
-            raise ValueError("rf_step: the first-order step has no history")
-    elif hist is None:
-        raise ValueError("rf_step: the second-order step needs hist")
-    if out is None:
-        out = torch.empty_like(x)
-    if order == 2 and hist_out is None:
-        hist_out = torch.empty_like(x)
+    _check_like("rf_step", x, u=u, hist=hist, out=out, hist_out=hist_out)
+    _check_f32("rf_step", coef6, 6, "coef6 holds six float32 values (1, t0, 1 - t0, t1, 1 - t1, cb)")
+    _check_order("rf_step", order, clip, scale, rows, hist, hist_out)
+    out = _like(x, out)
+    if order == 2:
+        hist_out = _like(x, hist_out)
     _C.call("adp_rf_step", ptr(x), ptr(u), ptr(hist), ptr(coef6), order, int(clip), ptr(scale), rows, per, ptr(out),
             ptr(hist_out), _C.stream())
     return out if order == 1 else (out, hist_out)
@@ -1029,16 +1036,10 @@ def edm_noise(x: Tensor, noise: Tensor, sigma: Tensor, sigma_data: float = 0.5, 
     item, sigma [B] (adp_edm_noise): what the preconditioned net reads and what it is trained towards.  x_in is the sampler's
     scaled state of x + sigma_r noise.  An output may be an input."""
     rows, per = _item_dims("edm_noise", x)
-    for name, other in (("noise", noise), ("x_in_out", x_in_out), ("target_out", target_out)):
-        if other is not None and other.shape != x.shape:
-            raise ValueError(f"edm_noise: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
-    if sigma.dtype != torch.float32 or sigma.numel() != rows:
-        raise ValueError(f"edm_noise: sigma holds one float32 value per item ({rows}); got {sigma.dtype} {tuple(sigma.shape)}")
+    _check_like("edm_noise", x, noise=noise, x_in_out=x_in_out, target_out=target_out)
+    _check_f32("edm_noise", sigma, rows, f"sigma holds one float32 value per item ({rows})")
     sd = _check_sigma_data("edm_noise", sigma_data)
-    if x_in_out is None:
-        x_in_out = torch.empty_like(x)
-    if target_out is None:
-        target_out = torch.empty_like(x)
+    x_in_out, target_out = _like(x, x_in_out), _like(x, target_out)
     _C.call("adp_edm_noise", ptr(x), ptr(noise), ptr(sigma), sd, rows, per, ptr(x_in_out), ptr(target_out), _C.stream())
     return x_in_out, target_out
 
@@ -1101,25 +1102,13 @@ def edm_step(xs: Tensor, f: Tensor, coef8: Tensor, rng4: Optional[Tensor] = None
     step's x0c), which a row with cb = 0 does not read.  A row with s1 = 0 does not read rng4, which may then be None (with
     s1 != 0 a missing row gives NaN).  Every output may be its input."""
     rows, per = _item_dims("edm_step", xs)
-    for name, other in (("f", f), ("hist", hist), ("out", out), ("hist_out", hist_out)):
-        if other is not None and other.shape != xs.shape:
-            raise ValueError(f"edm_step: {name} must have xs's shape {tuple(xs.shape)}; got {tuple(other.shape)}")
-    if coef8.dtype != torch.float32 or coef8.numel() != 8:
-        raise ValueError(f"edm_step: coef8 holds eight float32 values (a0, b0, e0, f0, c1, d1, s1, cb); got {coef8.dtype} "
-                         f"{tuple(coef8.shape)}")
-    if order not in (1, 2) or isinstance(order, bool):
-        raise ValueError(f"edm_step: order must be 1 or 2; got {order!r}")
-    _check_clip("edm_step", clip, scale, rows)
-    if order == 1:
-        if hist is not None or hist_out is not None:
-            raise ValueError("edm_step: the first-order step has no history")
-    elif hist is None:
-        raise ValueError("edm_step: the second-order step needs hist")
+    _check_like("edm_step", xs, "xs", f=f, hist=hist, out=out, hist_out=hist_out)
+    _check_f32("edm_step", coef8, 8, "coef8 holds eight float32 values (a0, b0, e0, f0, c1, d1, s1, cb)")
+    _check_order("edm_step", order, clip, scale, rows, hist, hist_out)
     row = None if rng4 is None else _rng_row_ptr("edm_step", rng4)
-    if out is None:
-        out = torch.empty_like(xs)
-    if order == 2 and hist_out is None:
-        hist_out = torch.empty_like(xs)
+    out = _like(xs, out)
+    if order == 2:
+        hist_out = _like(xs, hist_out)
     _C.call("adp_edm_step", ptr(xs), ptr(f), ptr(hist), ptr(coef8), row, order, int(clip), ptr(scale), rows, per, ptr(out),
             ptr(hist_out), _C.stream())
     return out if order == 1 else (out, hist_out)
@@ -1207,16 +1196,12 @@ def repaint_step(objective: str, x: Tensor, p: Tensor, source: Tensor, mask_u8: 
     does not read rng4, which may then be None (where a normal is needed a missing row gives NaN).  `out` may be x."""
     entry, words = _repaint_objective("repaint_step", objective)
     rows, per = _item_dims("repaint_step", x)
-    for name, other in (("p", p), ("source", source), ("mask", mask_u8), ("out", out)):
-        if other is not None and other.shape != x.shape:
-            raise ValueError(f"repaint_step: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
-    if row.dtype != torch.float32 or row.numel() != words + 4:
-        raise ValueError(f"repaint_step: row holds {words + 4} float32 values for objective {objective!r} (the step's "
-                         f"{words}, then A, S, P, Q); got {row.dtype} {tuple(row.shape)}")
+    _check_like("repaint_step", x, p=p, source=source, mask=mask_u8, out=out)
+    _check_f32("repaint_step", row, words + 4, f"row holds {words + 4} float32 values for objective {objective!r} (the "
+               f"step's {words}, then A, S, P, Q)")
     _check_clip("repaint_step", clip, scale, rows)
     rng = None if rng4 is None else _rng_row_ptr("repaint_step", rng4)
-    if out is None:
-        out = torch.empty_like(x)
+    out = _like(x, out)
     _C.call(entry, ptr(x), ptr(p), ptr(source), ptr(mask_u8, torch.uint8), ptr(row), rng, int(clip), ptr(scale), rows, per,
             ptr(out), _C.stream())
     return out
@@ -1252,25 +1237,21 @@ def distill_comb(x: Tensor, p: Tensor, coef: Tensor, q: Optional[Tensor] = None,
     """out = c0_r x + c1_r p [+ c2_r q] on x [B, ...] with one coefficient per item and term, coef [terms, B] float32 on the
     device, terms = 2 (no q) or 3 (adp_distill_comb).  `out` may be any input."""
     rows, per = _item_dims("distill_comb", x)
-    for name, other in (("p", p), ("q", q), ("out", out)):
-        if other is not None and other.shape != x.shape:
-            raise ValueError(f"distill_comb: {name} must have x's shape {tuple(x.shape)}; got {tuple(other.shape)}")
+    _check_like("distill_comb", x, p=p, q=q, out=out)
     terms = 2 if q is None else 3
     if coef.dtype != torch.float32 or tuple(coef.shape) != (terms, rows):
         raise ValueError(f"distill_comb: coef holds {terms} float32 coefficients per item, [{terms}, {rows}]"
                          f"{'' if q is not None else ' (no q: two terms)'}; got {coef.dtype} {tuple(coef.shape)}")
-    if out is None:
-        out = torch.empty_like(x)
+    out = _like(x, out)
     _C.call("adp_distill_comb", ptr(x), ptr(p), ptr(q), ptr(coef), terms, rows, per, ptr(out), _C.stream())
     return out
 
 
 def _check_wmse(what: str, v_pred: Tensor, v_target: Tensor, w: Optional[Tensor]) -> Tuple[int, int]:
     rows, per = _item_dims(what, v_pred)
-    if v_target.shape != v_pred.shape:
-        raise ValueError(f"{what}: v_target must have v_pred's shape {tuple(v_pred.shape)}; got {tuple(v_target.shape)}")
-    if w is not None and (w.dtype != torch.float32 or w.numel() != rows):
-        raise ValueError(f"{what}: w holds one float32 weight per item ({rows}); got {w.dtype} {tuple(w.shape)}")
+    _check_like(what, v_pred, "v_pred", v_target=v_target)
+    if w is not None:
+        _check_f32(what, w, rows, f"w holds one float32 weight per item ({rows})")
     if rows * per == 0:
         raise ValueError(f"{what}: the mean over no elements is undefined")
     return rows, per
